@@ -1,6 +1,6 @@
 """Headline benchmark: train images/sec of one full G+D step at 1024x1024 (BASELINE.json configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (N > 1, the driver's form)
 `python bench.py --gpus N` with N > 1 and no torchrun environment starts the N ranks itself (re-exec under
 torch.distributed.run on 127.0.0.1); rank 0 prints the line.
@@ -9,7 +9,12 @@ A step = SKITGModel.optimize_parameters on one synthetic batch (4 images / GPU, 
 patches each) that is already resident in HBM: generator forward, patch gather, D1 update,
 D2 update (incl. the reference's full-resolution visualisation pass), G update, three fused
 Adam steps.  LPIPS / CLIP terms are off (their weights cannot exist offline; stated in `config`).
-Rank 0 prints ONE JSON line with the extra `roofline` and `cpu_baseline` objects.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints it; the secondary
+figures (fresh-input steps, the `roofline` object, the `cpu_baseline` object, the inference leg, the `comm`
+block of a data-parallel run) are measured only with --full, and are null / absent otherwise.
+--dump-outputs DIR writes what the last timed step computed (losses, generated and discriminator outputs,
+updated weights) as DIR/<name>.npy; inputs, weights and random draws are seeded, so two builds can be
+compared output for output.
 """
 import argparse
 import json
@@ -77,6 +82,38 @@ def make_patch_batch(batch, rank, patch=32, height=None, width=None):
     from data.synthetic_dataset import make_patch_sample
 
     return default_collate([make_patch_sample(1234 + 100003 * rank + i, patch=patch, height=height, width=width) for i in range(batch)])
+
+
+DUMP_BYTES = 64 << 20     # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(model, out_dir, train):
+    """What the last timed step handed its caller, as float32 / float64 .npy files: every loss (loss_<name>.npy, float64), every
+    visual the step computed (the inputs real_* / M are left out) and, after a train step, each network's updated floating-point
+    state (weights_<net>.npy, its state_dict flattened in key order).  An array larger than its share of DUMP_BYTES is written as
+    a fixed, seeded sample of its flattened elements (the same indices in every run: they depend on the size alone)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    if train:
+        for k, v in model.get_current_losses().items():      # keys "l_<name>"
+            arrays["loss_" + k[2:]] = np.asarray(v, dtype=np.float64)
+    for k, v in model.get_current_visuals().items():
+        if torch.is_tensor(v) and v.is_floating_point() and not (k.startswith("real_") or k == "M"):
+            arrays[k] = v.detach()
+    if train:
+        for name in model.model_names:
+            sd = getattr(model, "net" + name).state_dict()
+            arrays["weights_" + name] = torch.cat([sd[k].detach().flatten().float() for k in sd if sd[k].is_floating_point()])
+    cap = (DUMP_BYTES - 65536) // 4 // max(1, len(arrays))     # elements per array (float32); the headers fit in the 64 KB kept aside
+    for k, v in arrays.items():
+        if torch.is_tensor(v):
+            if v.numel() > cap:
+                idx = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(0))[:cap].sort().values
+                v = v.flatten()[idx.to(v.device)]
+            v = v.float().cpu().numpy()
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def csrc_sha16():
@@ -366,8 +403,9 @@ def rccl_nranks(path):
     return max(found) if found else None
 
 
-def infer_measure(args, steps=None, warmup=None):
-    """Generator-only forward (test() of the model, BASELINE config 4: 16 images/GPU): seconds per step, images per step, the options"""
+def infer_measure(args, steps=None, warmup=None, dump=None):
+    """Generator-only forward (test() of the model, BASELINE config 4: 16 images/GPU): seconds per step, images per step, the options.
+    With `dump`, the last timed forward's outputs are written there (dump_outputs)."""
     batch_n = 16 if args.batch == 4 else args.batch
     steps, warmup = steps or args.steps, warmup or args.warmup
     model, opt = build_model(args.size, batch_n, args.model)
@@ -383,12 +421,15 @@ def infer_measure(args, steps=None, warmup=None):
     for _ in range(steps):
         model.test()
     torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / steps, batch_n, opt
+    dt = (time.perf_counter() - t0) / steps
+    if dump:
+        dump_outputs(model, dump, train=False)
+    return dt, batch_n, opt
 
 
 def infer_bench(args):
     """ms per image, inputs resident in HBM."""
-    dt, batch_n, opt = infer_measure(args)
+    dt, batch_n, opt = infer_measure(args, dump=args.dump_outputs)
     emit(json.dumps({
         "metric": "inference_ms_per_image", "value": dt / batch_n * 1e3, "unit": "ms/image", "n_gpus": 1,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt * 1e3, "higher_is_better": False,
@@ -433,9 +474,10 @@ def main():
     os.dup2(2, 1)
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    # defaults: the timed region is >= 1.5 s of steady state (20 steps = 0.14 s was too short for the driver's clock / gpu_busy sampling)
-    ap.add_argument("--steps", type=int, default=250)
-    ap.add_argument("--warmup", type=int, default=10)
+    # defaults: the timed region is >= 1.5 s of steady state (20 steps = 0.14 s was too short for the driver's clock / gpu_busy sampling);
+    # 250 / 10, or 30 / 4 with --lpips (~70 ms per step)
+    ap.add_argument("--steps", type=int, default=None)
+    ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--batch", type=int, default=4, help="images per GPU")
     ap.add_argument("--model", type=str, default="skitG")
@@ -445,7 +487,12 @@ def main():
     ap.add_argument("--p2p_h", type=int, default=0, help="pix2pixHD only: image height (with --p2p_w: BASELINE config 3 is --p2p_h 1024 --p2p_w 2048 --batch 1)")
     ap.add_argument("--p2p_w", type=int, default=0, help="pix2pixHD only: image width")
     ap.add_argument("--p2p_vgg", action="store_true", help="pix2pixHD only: keep the reference's default VGG19 feature loss on (seeded stand-in weights)")
-    ap.add_argument("--no_cpu_baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary figures after the timed steps: fresh-input steps, the per-kernel roofline and host "
+                         "enqueue probes, the CPU baseline, the inference leg and (data parallel) the exposed all-reduce time")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--no_cpu_baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--lpips", action="store_true",
                     help="SECONDARY workload: the same step with the reference's default LPIPS-VGG16 terms on (lambda_G1_lpips 1, lambda_G2_lpips 10; "
                          "stand-in VGG weights -- the arithmetic is the same): ~7.7 TFLOP of 3x3 convolutions per step on the GEMM-class kernels")
@@ -455,12 +502,20 @@ def main():
                          "asks for the rate with and without it; the default (and the headline) includes it")
     ap.add_argument("--infer", action="store_true",
                     help="measure the inference forward instead (BASELINE config 4: generator only, 16 images/GPU): ms per image")
-    ap.add_argument("--detail", type=str, default=None, help="write a per-(kernel, shape) timing table to this path")
+    ap.add_argument("--detail", type=str, default=None, help="with --full: write a per-(kernel, shape) timing table to this path")
     ap.add_argument("--train_only", action="store_true",
                     help="profiling form: warm-up + timed train steps on the resident batch and NOTHING else in the process (no fresh-input loop, "
                          "no per-launch event step, no host-enqueue probes, no CPU baseline, no inference leg), so that every kernel row of a "
                          "rocprofv3 / PMC pass over this command is launches-per-step x (warmup + steps) train-step launches")
     args = ap.parse_args()
+    if args.steps is None:
+        args.steps = 30 if args.lpips else 250
+    if args.warmup is None:
+        args.warmup = 4 if args.lpips else 10
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.detail and not args.full:
+        ap.error("--detail needs --full (the per-kernel table comes from the roofline leg)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args.gpus)
@@ -473,11 +528,15 @@ def main():
         raise SystemExit("bench.py: --gpus %d but the launcher started %d rank(s)" % (args.gpus, world))
     dev = torch.device("cuda", torch.cuda.current_device())
     torch.manual_seed(1234 + rank)      # per-rank DiffAugment draws (the default generator is seeded identically on every rank)
+    import random
+
+    import numpy as np
+
+    random.seed(1234 + rank)            # host-side draws ('more fake T' patch ranks, patch permutations): the same in every run
+    np.random.seed(1234 + rank)
     if args.infer:
         return infer_bench(args)
     model, opt = build_model(args.size, args.batch, args.model, netG=args.netG, lpips=args.lpips, p2p_vgg=args.p2p_vgg)
-    if args.lpips and args.steps == 250:
-        args.steps, args.warmup = 30, 4      # ~70 ms per step
     opt.use_hip_graph = not args.no_graph
     opt.skip_D2_visualisation_pass = bool(args.no_viz)
     style_dim = opt.style_code_dim if getattr(opt, "use_style_code", False) else 0
@@ -496,6 +555,8 @@ def main():
         model.optimize_parameters(epoch=1)
     barrier()
     ab = None
+    # Runs without --full too: it is tuning, not a secondary figure -- it picks the collective the timed steps then use (its own
+    # timings are reported only in the --full `comm` block)
     if ((world > 1 and os.environ.get("VTS_DDP_AB", "1") != "0") or (ddp.active() and os.environ.get("VTS_DDP_AB") == "force")) and "VTS_DDP_DIRECT" not in os.environ:
         ab = collective_ab(model, world, dev, barrier)      # torch.distributed all_reduce vs the library's reduce-scatter + all-gather
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]   # one event per step on the launch stream: spread, no sync
@@ -506,10 +567,12 @@ def main():
         marks[i + 1].record()
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, args.dump_outputs, train=True)
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     spread = {"min": per_step[0], "median": per_step[len(per_step) // 2], "max": per_step[-1], "p90": per_step[int(0.9 * (len(per_step) - 1))]}
     per_rank = None
-    if world > 1 or ddp.active():
+    if args.full and (world > 1 or ddp.active()):
         # every rank's own clock and device identity, gathered over the collective backend itself: a SCALE record then shows by itself
         # that N ranks on N different devices took part
         props = torch.cuda.get_device_properties(dev)
@@ -527,7 +590,7 @@ def main():
     # the same K steps with a FRESH host batch per step: set_input (H2D of S / I / M / patches, masking, candidate map) inside the timed
     # region, as a train.py loop pays it (`value` keeps the contract: inputs resident in HBM)
     fresh_ms = None
-    if world == 1 and args.model != "pix2pixHD" and not args.lpips and not args.train_only:
+    if args.full and world == 1 and args.model != "pix2pixHD" and not args.lpips and not args.train_only:
         def pinned(b):   # what the package's DataLoader hands over (data/__init__.py: pin_memory=True)
             return {k: (v.pin_memory() if torch.is_tensor(v) else v) for k, v in b.items()}
 
@@ -547,7 +610,7 @@ def main():
         fresh_ms = (time.perf_counter() - tf) / fresh_steps * 1e3
         model.set_input(batch, phase="train")
     comm = None
-    if world > 1 or ddp.active():
+    if args.full and (world > 1 or ddp.active()):
         # (VTS_DDP_FORCE=1 at one rank: the same block -- what the segmented schedule and the collectives' launch cost on one device)
         # exposed communication: the same K steps without the gradient all-reduces (the replicas drift apart: timing only, last)
         ddp.COMM_OFF = True
@@ -573,7 +636,7 @@ def main():
                 "ranks_gathered": len(per_rank) if per_rank else None, "nranks_seen": rccl_nranks(rccl_log), "collective_ab": ab}
 
     if rank == 0:
-        roof = kernel_roofline(model, batch, args.detail) if world == 1 and not args.train_only else None
+        roof = kernel_roofline(model, batch, args.detail) if args.full and world == 1 and not args.train_only else None
         if roof is not None:
             # host enqueue time of one step (no sync): tells whether the step is launch-bound
             for key, flag in (("host_enqueue_ms_eager", False), ("host_enqueue_ms", model.opt.use_hip_graph)):
@@ -585,11 +648,12 @@ def main():
                 torch.cuda.synchronize()
                 model.opt.use_hip_graph = keep
         cpu = None
-        if world == 1 and not args.no_cpu_baseline and args.model != "pix2pixHD" and not args.lpips and not args.train_only:
+        if args.full and world == 1 and not args.no_cpu_baseline and args.model != "pix2pixHD" and not args.lpips and not args.train_only:
             cpu = cpu_baseline(args.size, style_dim, netG=args.netG)
         ms = dt / args.steps * 1e3
         infer_ms = None
-        if world == 1 and args.model != "pix2pixHD" and not args.lpips and args.netG == "unet256_custom" and args.batch == 4 and not args.train_only:
+        if (args.full and world == 1 and args.model != "pix2pixHD" and not args.lpips and args.netG == "unet256_custom" and args.batch == 4
+                and not args.train_only):
             del model                       # (the 16-image forward builds its own model: BASELINE config 4)
             torch.cuda.empty_cache()
             idt, ib, _ = infer_measure(args, steps=50, warmup=5)
@@ -613,7 +677,7 @@ def main():
                                     else "LPIPS/CLIP terms off (no weights offline)"),
                 "global_batch": world * args.batch, "parallelism": "dp%d" % world, "losses_finite": finite,
                 "hip_graph": bool(opt.use_hip_graph), "d2_visualisation_pass": not args.no_viz,
-                "train_only": bool(args.train_only),
+                "train_only": bool(args.train_only), "full": bool(args.full),
             },
             "roofline": roof, "cpu_baseline": cpu,
         }

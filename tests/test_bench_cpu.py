@@ -21,3 +21,10 @@ def test_bench_rejects_world_size_mismatch():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"], cwd=ROOT, env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert r.returncode != 0 and "--gpus 2 but the launcher started 1 rank" in r.stderr.decode()
+
+
+def test_bench_rejects_bad_arguments_before_any_work():
+    """--steps below 1 and a per-kernel table without the --full legs that make it are refused at parse time"""
+    for extra in (["--steps", "0"], ["--detail", "table.txt"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+        assert r.returncode == 2 and r.stdout.decode().strip() == "", (extra, r.stderr.decode()[-2000:])

@@ -15,9 +15,10 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(extra, env_extra, want_stderr=False):
+def _bench(extra, env_extra, want_stderr=False, full=True):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", **env_extra)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "3"] + (["--no_cpu_baseline"] if env_extra else []) + extra,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "3"] + (["--full"] if full else []) +
+                       (["--no_cpu_baseline"] if env_extra else []) + extra,
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
@@ -100,3 +101,32 @@ def test_bench_line_schema():
     assert {"bound", "achieved", "peak", "unit", "frac", "traffic"} <= set(out["roofline"]) and out["roofline"]["bound"] in ("hbm", "mfma")
     assert abs(out["roofline"]["frac"] - out["roofline"]["achieved"] / out["roofline"]["peak"]) < 1e-9
     assert abs(out["value"] - out["n_gpus"] * 1 * 1e3 / out["ms_per_step"]) < 1e-6 * out["value"]
+
+
+def test_plain_bench_line_and_dump_outputs(tmp_path):
+    """a plain run (no --full) prints the headline keys with the secondary figures left out, and --dump-outputs writes the last timed
+    step's losses, outputs and weights as float32 / float64 arrays within 64 MB.  The runs are repeatable and --steps sets the number of
+    steps taken: 3 warm-up + 5 timed steps and, in another process, 4 + 4 give the same dump; 3 + 6 gives another one"""
+    import numpy as np
+
+    def run(warmup, steps):
+        d = tmp_path / ("w%d_s%d" % (warmup, steps))
+        out = _bench(["--size", "256", "--batch", "1", "--warmup", str(warmup), "--steps", str(steps), "--dump-outputs", str(d)], {}, full=False)
+        assert out["steps"] == steps and out["warmup"] == warmup and out["ms_per_step"] > 0
+        return out, {f: np.load(os.path.join(str(d), f)) for f in sorted(os.listdir(str(d)))}, d
+
+    out, a, d = run(3, 5)
+    assert out["metric"] == "train_images_per_sec" and out["unit"] == "images/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert out["config"]["full"] is False
+    assert out["roofline"] is None and out["cpu_baseline"] is None and out["inference_ms_per_image"] is None and "comm" not in out
+    assert {"loss_G_GAN.npy", "fake_I.npy", "weights_G.npy", "weights_D.npy", "weights_D2.npy"} <= set(a), sorted(a)
+    assert not any(f.startswith("real_") for f in a)
+    assert sum(os.path.getsize(os.path.join(str(d), f)) for f in a) <= 64 << 20
+    for f, v in a.items():
+        assert v.dtype in (np.float32, np.float64) and np.isfinite(v).all(), f
+    _, b, _ = run(4, 4)
+    assert sorted(b) == sorted(a)
+    for f in a:      # same seeded inputs and draws, same 8 steps (tolerance: reductions may use atomics)
+        np.testing.assert_allclose(b[f], a[f], rtol=1e-4, atol=1e-5, err_msg=f)
+    _, c, _ = run(3, 6)
+    assert any(not np.allclose(c[f], a[f], rtol=1e-3, atol=1e-5) for f in a), "one more timed step changed nothing"

@@ -678,12 +678,38 @@ typedef struct vts_unet_desc {
 int64_t vts_unet_forward_ws_floats(const vts_unet_desc* d);
 int vts_unet_forward(const vts_unet_desc* d, float* ws, int64_t ws_floats, void* stream);
 
+/* The generator's backward as ONE call (`vts_unet_bwd`): the schedule of vts/engine.py:unet_backward, launch for launch.
+ * Workspace contract: vts_unet_backward reads what vts_unet_forward left in `ws` for the SAME descriptor (raw layer outputs, the
+ * [scale, shift, mean, rstd] block of every normalised layer) -- nothing is recomputed.  vts_unet_backward_ws_floats(d) >=
+ * vts_unet_forward_ws_floats(d) and the forward's region is its prefix: allocate the backward size once and pass that buffer to both
+ * calls (the forward accepts a larger one).  Between the two calls the caller must not touch the workspace, the weights or the input.
+ *   d_raw          [N][out_c][H][W] d loss / d pre-Tanh output of up0 (visual channels) ++ up0_T (tactile), batch stride d_raw_nstride
+ *                  (0: contiguous) -- what vts_g_out_grad produces
+ *   *_dw / *_db    every parameter gradient of the layers that exist is OVERWRITTEN (a bias in front of an InstanceNorm gets exact
+ *                  zeros: its gradient is identically zero); a *_db may be NULL only where the forward descriptor has no bias.  The
+ *                  weight-gradient partials are reduced in fixed order by one vts_wgrad_reduce_batch at the end (deterministic).
+ * No gradient w.r.t. the network input or the tiled style code is formed (its channels of up_{num_downs-1}'s weight gradient are).
+ * d->side_stream runs the tactile branch's layers beside the visual branch (events: capturable); the two branches' contributions to the
+ * shared tensors are summed in a fixed order, so the result is the same bits with or without a side stream. */
+typedef struct vts_unet_grads {
+  const float* d_raw;
+  int64_t d_raw_nstride;
+  float* down_dw[VTS_UNET_MAX_DOWNS];
+  float* down_db[VTS_UNET_MAX_DOWNS];
+  float* up_dw[VTS_UNET_MAX_DOWNS];
+  float* up_db[VTS_UNET_MAX_DOWNS];
+  float* upT_dw[VTS_UNET_MAX_DOWNS];
+  float* upT_db[VTS_UNET_MAX_DOWNS];
+} vts_unet_grads;
+int64_t vts_unet_backward_ws_floats(const vts_unet_desc* d);
+int vts_unet_backward(const vts_unet_desc* d, const vts_unet_grads* g, float* ws, int64_t ws_floats, void* stream);
+
 /* ---- network-level entries: the discriminators' forward (round 6; SURVEY.md 8(b): `vts_msd_fwd`; csrc/vts_msd.cpp) ---------------------
  * vts_patchgan_forward = NLayerDiscriminator.forward (models/networks.py:1696-1750), vts_msd_forward = MultiscaleDiscriminator.forward
  * (models/networks.py:1649-1691: num_D PatchGANs over an AvgPool2d(3, 2, 1, count_include_pad False) pyramid, full resolution first), in
  * TRAINING mode -- BatchNorm2d normalises with the batch statistics and advances its running statistics (momentum, unbiased variance,
  * num_batches_tracked += 1), as every discriminator call of a reference training step does (models/sinskitG_model.py:1361, 1374, 1490,
- * 1567, 1584, 1781) -- forward only: nothing is kept for a backward.  Weights in the reference's state-dict layout
+ * 1567, 1584, 1781).  The workspace keeps what vts_patchgan_backward / vts_msd_backward read (below).  Weights in the reference's state-dict layout
  * (layer<k>.<i>.weight [Cout, Cin, 4, 4]).  Convolution j: Conv2d(4, stride[j], padding 2); LeakyReLU(0.2) in front of every convolution
  * but the first; BatchNorm2d behind convolution j where gamma[j] / beta[j] are given (never the first or the last).
  *   running_mean / running_var / num_batches_tracked [j]   NULL: this call does not advance the running statistics
@@ -723,6 +749,40 @@ typedef struct vts_msd_desc {
 } vts_msd_desc;
 int64_t vts_msd_forward_ws_floats(const vts_msd_desc* d);
 int vts_msd_forward(const vts_msd_desc* d, float* ws, int64_t ws_floats, void* stream);
+
+/* The discriminators' backward as ONE call (`vts_msd_bwd`): vts/engine.py:_msd_scale_backward / msd_backward, launch for
+ * launch.  Workspace contract: the backward reads the pyramid levels, raw layer outputs and BatchNorm statistics that a vts_patchgan_forward
+ * / vts_msd_forward call with the SAME descriptor and run_head = 1 left in `ws`; vts_*_backward_ws_floats(d) >= the forward's size and the
+ * forward's region is its prefix (allocate the backward size once, pass it to both).  The running statistics are not touched.
+ *   dpred                       d loss / d prediction map [N, 1, h, w] of the scale (required)
+ *   dw / db / dgamma / dbeta    parameter gradients per convolution (db where the convolution has a bias, dgamma / dbeta where it has a
+ *                               BatchNorm); ALL NULL: input gradient only (the generator step).  accumulate = 1 adds into them (the D
+ *                               update sums its real and fake passes); otherwise they are overwritten, and the bias of a convolution in
+ *                               front of a BatchNorm gets exact zeros (its gradient is identically zero)
+ *   d_in, d_in_accumulate       optional [N, C, H, W] gradient w.r.t. in1, or w.r.t. in0 when in1.C == 0; for vts_msd_backward summed
+ *                               over the pyramid as d0 + pool^T(d1 + pool^T(d2 ...)) (the per-scale d_in fields are ignored there)
+ * Wide layers take the GEMM-class kernels on weights packed into the workspace exactly where engine.py:_flat4 sends them.  The scales run
+ * one after the other on `stream`. */
+typedef struct vts_patchgan_grads {
+  const float* dpred;
+  float* dw[VTS_PATCHGAN_MAX_CONVS];
+  float* db[VTS_PATCHGAN_MAX_CONVS];
+  float* dgamma[VTS_PATCHGAN_MAX_CONVS];
+  float* dbeta[VTS_PATCHGAN_MAX_CONVS];
+  int accumulate;
+  float* d_in;
+  int d_in_accumulate;
+} vts_patchgan_grads;
+int64_t vts_patchgan_backward_ws_floats(const vts_patchgan_desc* d);
+int vts_patchgan_backward(const vts_patchgan_desc* d, const vts_patchgan_grads* g, float* ws, int64_t ws_floats, void* stream);
+
+typedef struct vts_msd_grads {
+  vts_patchgan_grads scale[VTS_MSD_MAX_SCALES];
+  float* d_in;
+  int d_in_accumulate;
+} vts_msd_grads;
+int64_t vts_msd_backward_ws_floats(const vts_msd_desc* d);
+int vts_msd_backward(const vts_msd_desc* d, const vts_msd_grads* g, float* ws, int64_t ws_floats, void* stream);
 
 /* ---- optional collective of the data-parallel path (csrc/vts_comm.cpp; off by default, vts/ddp.py: VTS_DDP_DIRECT=1) ----------------
  * Sum-all-reduce of one flat fp32 gradient bucket as reduce-scatter + all-gather on the library's OWN RCCL communicator and side stream

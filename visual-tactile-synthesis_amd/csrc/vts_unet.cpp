@@ -180,13 +180,14 @@ extern "C" int64_t vts_unet_forward_ws_floats(const vts_unet_desc* d) {
 
 // fork / join events of the two-lane form (created once per host thread; recorded and waited on inside the caller's stream order, so the
 // call stays capturable into a HIP graph)
-static int lane_events(hipEvent_t* fork, hipEvent_t* join) {
-  static thread_local hipEvent_t ev[2] = {nullptr, nullptr};
-  if (!ev[0]) {
-    VTS_CHECK_HIP(hipEventCreateWithFlags(&ev[0], hipEventDisableTiming));
-    VTS_CHECK_HIP(hipEventCreateWithFlags(&ev[1], hipEventDisableTiming));
+// (set 0: the forward, set 1: the backward -- a graph that captures both records each pair once)
+static int lane_events(hipEvent_t* fork, hipEvent_t* join, int set = 0) {
+  static thread_local hipEvent_t ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+  if (!ev[set][0]) {
+    VTS_CHECK_HIP(hipEventCreateWithFlags(&ev[set][0], hipEventDisableTiming));
+    VTS_CHECK_HIP(hipEventCreateWithFlags(&ev[set][1], hipEventDisableTiming));
   }
-  *fork = ev[0]; *join = ev[1];
+  *fork = ev[set][0]; *join = ev[set][1];
   return VTS_OK;
 }
 
@@ -251,4 +252,337 @@ extern "C" int vts_unet_forward(const vts_unet_desc* d, float* ws, int64_t ws_fl
     if (rc != VTS_OK) return finish(rc);
   }
   return finish(VTS_OK);
+}
+
+// ---- the backward (`vts_unet_bwd`): vts/engine.py:_unet_backward / _unet_backward_encoder as one call ---------------------
+// Reads the forward's Plan region of `ws` (raw outputs, statistics); everything the backward itself needs is carved out behind it, one
+// region per buffer and per launch (gradient maps, k-split / statistics scratch, epilogue sums, weight-gradient partials), so nothing is
+// shared between the two lanes and the region list is the same in the sizing pass and in the launching pass.  The schedule:
+//   decoder lanes  lane b = 0 (visual, `stream`) / 1 (tactile, side stream): up_i / up_i_T for i = 0 .. nls-1, each lane into its own
+//                  buffers; then their two contributions to the shared tensors (the skip features 1 .. nls-1, the gradient w.r.t. the
+//                  trunk's output) are summed as engine.py's total(a, b): vts_pad_affine(a, res = b)
+//   trunk          up_i for i = nls .. nd-1
+//   encoder        down_i for i = nd-1 .. 0
+//   one vts_wgrad_reduce_batch over the deferred weight-gradient partials of all of them
+// Per up block (engine.py:up_bwd): InstanceNorm backward of the output gradient (skipped where the producing convolution's k-split
+// epilogue applied it, vts_norm_bwd_from_partials where its tiled epilogue left the sums), the deferred weight gradient on
+// cat(input, skip | style), the bias gradient of the outermost block, the backward-data convolution into the input's gradient with
+// bwd_sums "in" (not at the innermost block nor at the split point i == nls-1, where the two lanes' parts are summed first), and the
+// skip feature's gradient through the skip slice of the weight.
+namespace {
+
+struct Bwd {
+  const vts_unet_desc* d;
+  const vts_unet_grads* g;
+  float* ws;
+  const Plan* P;
+  const Layer* L;
+  bool dry;                         // sizing pass: regions are taken, nothing is launched
+  int64_t off;
+  vts_reduce_job jobs[3 * VTS_UNET_MAX_DOWNS];
+  int njobs;
+
+  float* take(int64_t n) {
+    float* p = ws + off;
+    off += (n + 63) / 64 * 64;
+    return p;
+  }
+};
+
+// a gradient map and what its producing convolution left for the normalisation backward that reads it next
+struct Grad {
+  float* data;
+  int C;
+  int64_t nstride;
+  int slots;                        // -1: InstanceNorm backward already applied; > 0: epilogue sums in `part`; 0: none
+  float* part;
+};
+
+vts_operand plain(const float* p, int C, int64_t nstride) {
+  vts_operand o{};
+  o.data = p; o.C = C; o.nstride = nstride;
+  return o;
+}
+
+int64_t hw_at(const vts_unet_desc* d, int s) { return (int64_t)(d->H >> s) * (d->W >> s); }
+
+// InstanceNorm2d backward of g in place, against the layer output x (raw) with statistics block `stat` (engine.py / ops.norm_bwd)
+int norm_bwd_in(Bwd& B, Grad& g, const float* x, int64_t x_nstride, int HW, const float* stat, void* st) {
+  const int64_t NC = (int64_t)B.d->N * g.C;
+  vts_norm_bwd_desc nb{};
+  nb.dy = g.data; nb.x = x; nb.nstride = x_nstride; nb.N = B.d->N; nb.C = g.C; nb.HW = HW; nb.mode = 0;
+  nb.mean = stat + 2 * NC; nb.rstd = stat + 3 * NC; nb.ngroups = 1;
+  float* nws = B.take(vts_norm_ws_floats(B.d->N, g.C, HW));
+  if (B.dry) return VTS_OK;
+  const int slots = g.slots;
+  g.slots = 0;
+  if (slots == -1) return VTS_OK;
+  if (slots > 0) return vts_norm_bwd_from_partials(&nb, g.part, slots, nullptr, st);
+  return vts_norm_bwd(&nb, nws, st);
+}
+
+// the backward-data convolution (vts_conv4x4 / with bwd_sums "in": vts_conv4x4_bsums), k-split scratch for small maps
+int conv_bwd(Bwd& B, vts_conv_desc& c, bool bsums, Grad* out, void* st) {
+  if ((int64_t)c.OH * c.OW <= 64 * 64) {
+    c.ws_floats = vts_conv4x4_ws_floats(&c);
+    c.ws = B.take(c.ws_floats);
+  }
+  if (!bsums) {
+    if (out) out->slots = 0;
+    return B.dry ? VTS_OK : vts_conv4x4(&c, st);
+  }
+  const int64_t pf = vts_conv4x4_norm_ws_floats(&c);
+  float* part = B.take(pf);
+  if (B.dry) return VTS_OK;
+  int slots = -1;                   // the normalisation behind `out` is InstanceNorm2d(affine=False)
+  const int rc = vts_conv4x4_bsums(&c, part, pf, &slots, st);
+  out->slots = slots; out->part = part;
+  return rc;
+}
+
+// deferred weight gradient: partials into a region of their own, one reduce job
+int wgrad(Bwd& B, vts_wgrad_desc& w, void* st) {
+  w.defer = 1; w.accumulate = 0;
+  const int64_t n = vts_wgrad4x4_ws_floats(&w);
+  float* part = B.take(n);
+  const int64_t nel = (int64_t)(w.lo0.C + w.lo1.C) * (w.hi0.C + w.hi1.C) * 16;
+  if (B.dry) return VTS_OK;
+  vts_reduce_job& j = B.jobs[B.njobs++];
+  j = vts_reduce_job{};
+  j.dw = w.dw; j.nel = nel; j.accumulate = 0; j.nseg = 1; j.part[0] = part; j.pw[0] = (int)(n / nel);
+  return vts_wgrad4x4(&w, part, st);
+}
+
+int bias_sum(Bwd& B, const Grad& g, int HW, float* db, void* st) {
+  float* cws = B.take(vts_channel_sum_ws_floats(B.d->N, g.C, HW));
+  if (B.dry || !db) return VTS_OK;
+  return vts_channel_sum(g.data, g.nstride, B.d->N, g.C, HW, db, 0, cws, nullptr, st);
+}
+
+// engine.py:up_bwd for block i of branch b: gin = gradient w.r.t. the block's output (normalised for i > 0), into `tin` (gradient w.r.t.
+// the block's input) and `tskip` (w.r.t. its skip feature)
+int up_bwd(Bwd& B, int b, int i, Grad& gin, Grad* tin, Grad* tskip, bool bsums, void* st) {
+  const vts_unet_desc* d = B.d;
+  const int nd = d->num_downs, nls = d->num_layer_separate;
+  const Layer& l = B.L[b ? 2 * nd + (nls - 1 - i) : nd + (nd - 1 - i)];
+  const vts_conv_desc& f = l.c;     // the forward convolution of this block
+  const int cout = l.C;
+  const int ohw = f.OH * f.OW;
+  int rc;
+  if (i != 0 && (rc = norm_bwd_in(B, gin, f.out, f.out_nstride, ohw, B.ws + l.stat, st)) != VTS_OK) return rc;
+  vts_wgrad_desc w{};
+  w.lo0 = f.in0; w.lo1 = f.in1; w.hi0 = plain(gin.data, cout, gin.nstride);
+  w.act_lo = VTS_ACT_RELU; w.act_hi = VTS_ACT_NONE;
+  w.N = d->N; w.LH = f.IH; w.LW = f.IW; w.HH = f.OH; w.HW = f.OW; w.stride = 2; w.pad = 1;
+  w.dw = b ? B.g->upT_dw[i] : B.g->up_dw[i];
+  if ((rc = wgrad(B, w, st)) != VTS_OK) return rc;
+  if (i == 0 && (rc = bias_sum(B, gin, ohw, b ? B.g->upT_db[0] : B.g->up_db[0], st)) != VTS_OK) return rc;
+  const int cin0 = f.in0.C;
+  vts_conv_desc c{};
+  c.in0 = plain(gin.data, cout, gin.nstride);
+  c.N = d->N; c.IH = f.OH; c.IW = f.OW; c.OH = f.IH; c.OW = f.IW; c.Cout = cin0;
+  c.stride = 2; c.pad = 1; c.transposed = 0;
+  c.w = f.w; c.ws_co = cout * 16; c.ws_ci = 16;
+  c.out = tin->data; c.out_nstride = tin->nstride;
+  c.dmask = f.in0; c.dmask_act = VTS_ACT_RELU;
+  if ((rc = conv_bwd(B, c, bsums, tin, st)) != VTS_OK) return rc;
+  if (i != 0 && i != nd - 1) {      // the skip connection: its slice of the weight, into the skip feature's gradient
+    vts_conv_desc s = c;
+    s.ws = nullptr; s.ws_floats = 0;
+    s.w = f.w + (int64_t)cin0 * cout * 16; s.Cout = f.in1.C;
+    s.out = tskip->data; s.out_nstride = tskip->nstride;
+    s.dmask = f.in1;
+    if ((rc = conv_bwd(B, s, false, tskip, st)) != VTS_OK) return rc;
+  }
+  return VTS_OK;
+}
+
+int bwd_check(const vts_unet_desc* d, const vts_unet_grads* g) {
+  const int rc = check(d);
+  if (rc != VTS_OK) return rc;
+  VTS_CHECK_ARG(g, "vts_unet_backward: null gradient struct");
+  VTS_CHECK_ARG(g->d_raw, "vts_unet_backward: null d_raw");
+  const int nd = d->num_downs, nls = d->num_layer_separate;
+  const int out_c = d->up_cout[0] + (nls > 0 ? d->upT_cout[0] : 0);
+  VTS_CHECK_ARG(g->d_raw_nstride == 0 || g->d_raw_nstride >= (int64_t)out_c * d->H * d->W, "vts_unet_backward: d_raw_nstride %lld below %d x %d x %d",
+                (long long)g->d_raw_nstride, out_c, d->H, d->W);
+  for (int i = 0; i < nd; ++i) {
+    VTS_CHECK_ARG(g->down_dw[i] && (!d->down_b[i] || g->down_db[i]), "vts_unet_backward: down%d gradient missing (down_dw / down_db[%d])", i, i);
+    VTS_CHECK_ARG(g->up_dw[i] && (!d->up_b[i] || g->up_db[i]), "vts_unet_backward: up%d gradient missing (up_dw / up_db[%d])", i, i);
+    VTS_CHECK_ARG(i >= nls || (g->upT_dw[i] && (!d->upT_b[i] || g->upT_db[i])), "vts_unet_backward: up%d_T gradient missing (upT_dw / upT_db[%d])", i, i);
+    // the grid of vts_pad_affine (the lanes' sum) carries (n, c) in 16 bits
+    VTS_CHECK_ARG((int64_t)d->N * d->channels[i] <= 65535, "vts_unet_backward: N x channels[%d] = %lld above 65535", i, (long long)d->N * d->channels[i]);
+  }
+  return VTS_OK;
+}
+
+// the whole schedule; `sync` = (fork, join) events when the tactile lane runs on the side stream
+int run_bwd(Bwd& B, void* stream, void* side, hipEvent_t fork, hipEvent_t join) {
+  const vts_unet_desc* d = B.d;
+  const vts_unet_grads* g = B.g;
+  const int nd = d->num_downs, nls = d->num_layer_separate;
+  const int N = d->N;
+  auto map = [&](int i) {           // a gradient buffer shaped like feats[i] / the input of up_i: [N][channels[i]][H >> (i+1)][W >> (i+1)]
+    Grad r{};
+    r.C = d->channels[i]; r.nstride = (int64_t)r.C * hw_at(d, i + 1);
+    r.data = B.take(N * r.nstride);
+    return r;
+  };
+  Grad dfeat[VTS_UNET_MAX_DOWNS], dxs[VTS_UNET_MAX_DOWNS], dxl[2][VTS_UNET_MAX_DOWNS], dfl[2][VTS_UNET_MAX_DOWNS];
+  for (int i = 0; i < nd; ++i) {
+    dfeat[i] = map(i);
+    dxs[i] = i < nd - 1 ? map(i) : Grad{};
+    for (int b = 0; b < 2; ++b) {
+      dxl[b][i] = i < nls ? map(i) : Grad{};
+      dfl[b][i] = (i > 0 && i < nls) ? map(i) : Grad{};
+    }
+  }
+  const int out_c = d->up_cout[0] + (nls > 0 ? d->upT_cout[0] : 0);
+  const int64_t raw_ns = g->d_raw_nstride ? g->d_raw_nstride : (int64_t)out_c * d->H * d->W;
+  int rc;
+  // biases in front of an InstanceNorm: exact zeros (every gradient pointer is overwritten)
+  if (!B.dry) {
+    bool ok = true;
+    auto zero = [&](float* p, int n) { ok = ok && (!p || hipMemsetAsync(p, 0, sizeof(float) * n, (hipStream_t)stream) == hipSuccess); };
+    for (int i = 1; i < nd; ++i) {
+      if (i < nd - 1) zero(g->down_db[i], d->channels[i]);
+      zero(g->up_db[i], d->up_cout[i]);
+      if (i < nls) zero(g->upT_db[i], d->upT_cout[i]);
+    }
+    if (!ok) {
+      vts_set_error("vts_unet_backward: zeroing the bias gradients failed");
+      return VTS_ERR_LAUNCH;
+    }
+  }
+  // decoder lanes: lane 1 (tactile) first on the side stream, then lane 0 on `stream` (engine.py:_run_lanes)
+  auto lane = [&](int b, void* st) {
+    for (int i = 0; i < nls; ++i) {
+      Grad gin{};
+      if (i == 0) {
+        gin.data = const_cast<float*>(g->d_raw) + (b ? (int64_t)d->up_cout[0] * d->H * d->W : 0);
+        gin.C = b ? d->upT_cout[0] : d->up_cout[0]; gin.nstride = raw_ns;
+      } else {
+        gin = dxl[b][i - 1];
+      }
+      const int r = up_bwd(B, b, i, gin, &dxl[b][i], &dfl[b][i], i != nls - 1, st);
+      if (r != VTS_OK) return r;
+      if (i > 0) dxl[b][i - 1] = gin;
+    }
+    return (int)VTS_OK;
+  };
+  bool forked = false;
+  auto finish = [&](int r) {
+    if (forked && (hipEventRecord(join, (hipStream_t)side) != hipSuccess || hipStreamWaitEvent((hipStream_t)stream, join, 0) != hipSuccess) && r == VTS_OK) {
+      vts_set_error("vts_unet_backward: joining the side stream failed");
+      return (int)VTS_ERR_LAUNCH;
+    }
+    return r;
+  };
+  if (nls > 0) {
+    if (side && !B.dry) {
+      if (hipEventRecord(fork, (hipStream_t)stream) != hipSuccess || hipStreamWaitEvent((hipStream_t)side, fork, 0) != hipSuccess) {
+        vts_set_error("vts_unet_backward: forking the side stream failed");
+        return VTS_ERR_LAUNCH;
+      }
+      forked = true;
+    }
+    if ((rc = lane(1, side ? side : stream)) != VTS_OK) return finish(rc);
+    if ((rc = lane(0, stream)) != VTS_OK) return finish(rc);
+    if ((rc = finish(VTS_OK)) != VTS_OK) return rc;
+    forked = false;
+    // total(a, b) = a + b into the shared buffers (ops.pad_affine with res)
+    auto total = [&](const Grad& a, const Grad& bb, Grad& dst, int s) {
+      if (B.dry) return (int)VTS_OK;
+      vts_operand o = plain(a.data, a.C, a.nstride);
+      dst.slots = 0;
+      return vts_pad_affine(&o, N, d->H >> s, d->W >> s, 0, 0, 0, 0, 0, VTS_ACT_NONE, bb.data, dst.data, 0, stream);
+    };
+    for (int i = 1; i < nls; ++i)
+      if ((rc = total(dfl[0][i], dfl[1][i], dfeat[i], i + 1)) != VTS_OK) return rc;
+    if ((rc = total(dxl[0][nls - 1], dxl[1][nls - 1], dxs[nls - 1], nls)) != VTS_OK) return rc;
+  }
+  // the shared trunk (everything when nls == 0)
+  for (int i = nls; i < nd; ++i) {
+    Grad gin{};
+    if (i == 0) {
+      gin.data = const_cast<float*>(g->d_raw); gin.C = d->up_cout[0]; gin.nstride = raw_ns;
+    } else {
+      gin = dxs[i - 1];
+    }
+    Grad* tin = i == nd - 1 ? &dfeat[nd - 1] : &dxs[i];
+    if ((rc = up_bwd(B, 0, i, gin, tin, &dfeat[i], i != nd - 1 && !(nls > 0 && i == nls - 1), stream)) != VTS_OK) return rc;
+    if (i > 0) dxs[i - 1] = gin;
+  }
+  // the encoder
+  for (int i = nd - 1; i >= 0; --i) {
+    const Layer& l = B.L[i];
+    const vts_conv_desc& f = l.c;
+    Grad& gi = dfeat[i];
+    const int ohw = f.OH * f.OW;
+    if (l.normed && (rc = norm_bwd_in(B, gi, f.out, f.out_nstride, ohw, B.ws + l.stat, stream)) != VTS_OK) return rc;
+    vts_wgrad_desc w{};
+    w.lo0 = plain(gi.data, gi.C, gi.nstride); w.hi0 = f.in0; w.hi1 = f.in1;
+    w.act_lo = VTS_ACT_NONE; w.act_hi = i ? VTS_ACT_LRELU : VTS_ACT_NONE;
+    w.N = N; w.LH = f.OH; w.LW = f.OW; w.HH = f.IH; w.HW = f.IW; w.stride = 2; w.pad = 1;
+    w.dw = g->down_dw[i];
+    if ((rc = wgrad(B, w, stream)) != VTS_OK) return rc;
+    if (!l.normed && (rc = bias_sum(B, gi, ohw, g->down_db[i], stream)) != VTS_OK) return rc;
+    if (i > 0) {
+      vts_conv_desc c{};
+      c.in0 = plain(gi.data, gi.C, gi.nstride);
+      c.N = N; c.IH = f.OH; c.IW = f.OW; c.OH = f.IH; c.OW = f.IW; c.Cout = f.in0.C;
+      c.stride = 2; c.pad = 1; c.transposed = 1;
+      c.w = f.w; c.ws_co = 16; c.ws_ci = f.in0.C * 16;
+      c.out = dfeat[i - 1].data; c.out_nstride = dfeat[i - 1].nstride;
+      c.dmask = f.in0; c.dmask_act = VTS_ACT_LRELU;
+      c.accumulate = i - 1 > 0;     // dfeat[i-1] already holds the skip contribution of up_{i-1}
+      if ((rc = conv_bwd(B, c, i - 1 > 0, &dfeat[i - 1], stream)) != VTS_OK) return rc;
+    }
+  }
+  if (B.dry) return VTS_OK;
+  return vts_wgrad_reduce_batch(B.jobs, B.njobs, stream);
+}
+
+int64_t bwd_total(const vts_unet_desc* d, const vts_unet_grads* g, const Plan& P) {
+  Layer L[3 * VTS_UNET_MAX_DOWNS];
+  int n = 0;
+  float* base = reinterpret_cast<float*>(uintptr_t(4096));
+  build(d, base, P, L, &n);
+  Bwd B{};
+  B.d = d; B.g = g; B.ws = base; B.P = &P; B.L = L; B.dry = true; B.off = P.total;
+  run_bwd(B, nullptr, nullptr, nullptr, nullptr);
+  return B.off;
+}
+
+}  // namespace
+
+extern "C" int64_t vts_unet_backward_ws_floats(const vts_unet_desc* d) {
+  if (check(d) != VTS_OK) return -1;
+  Plan P{};
+  plan(d, P);
+  vts_unet_grads g{};              // sizes only depend on the descriptor
+  g.d_raw = reinterpret_cast<const float*>(uintptr_t(4096));
+  return bwd_total(d, &g, P);
+}
+
+extern "C" int vts_unet_backward(const vts_unet_desc* d, const vts_unet_grads* g, float* ws, int64_t ws_floats, void* stream) {
+  const int rc0 = bwd_check(d, g);
+  if (rc0 != VTS_OK) return rc0;
+  Plan P{};
+  plan(d, P);
+  const int64_t need = bwd_total(d, g, P);
+  VTS_CHECK_ARG(ws && ws_floats >= need, "vts_unet_backward: workspace of %lld floats, need %lld (vts_unet_backward_ws_floats)", (long long)ws_floats,
+                (long long)need);
+  Layer L[3 * VTS_UNET_MAX_DOWNS];
+  int n = 0;
+  build(d, ws, P, L, &n);
+  const bool lanes = d->side_stream && d->side_stream != stream && d->num_layer_separate > 0;
+  hipEvent_t fork = nullptr, join = nullptr;
+  if (lanes) {
+    const int rc = lane_events(&fork, &join, 1);
+    if (rc != VTS_OK) return rc;
+  }
+  Bwd B{};
+  B.d = d; B.g = g; B.ws = ws; B.P = &P; B.L = L; B.dry = false; B.off = P.total;
+  return run_bwd(B, stream, lanes ? d->side_stream : nullptr, fork, join);
 }

@@ -253,6 +253,49 @@ def unet_forward_c(G, x, style_tile=None, g_out=None, side_stream=None):
     return g_out
 
 
+def unet_forward_train_c(G, x, style_tile=None, side_stream=None):
+    """the forward through vts_unet_forward into a workspace sized for vts_unet_backward (include/vts.h: the forward's region is its
+    prefix): returns (g_out, ctx) for unet_backward_c.  Not the product's path (the training step keeps the Python schedule)."""
+    lib = L.load()
+    x0 = _as_act(x[0] if isinstance(x, (tuple, list)) else x)
+    n, _, h, w = x0.data.shape
+    oc = G.up0.conv.weight.shape[1] + (G.up0_T.conv.weight.shape[1] if G.num_layer_separate > 0 else 0)
+    g_out = _empty(n, oc, h, w, x0.data.device)
+    d = unet_desc(G, x, g_out, style_tile, side_stream)
+    need = int(lib.vts_unet_backward_ws_floats(C.byref(d)))
+    if need < 0:
+        raise RuntimeError("vts_unet_backward_ws_floats: %s" % lib.vts_last_error().decode())
+    ws = torch.empty(need, dtype=torch.float32, device=x0.data.device)
+    L.check(lib.vts_unet_forward(C.byref(d), ws.data_ptr(), ws.numel(), L.stream()), "vts_unet_forward")
+    return g_out, (x, style_tile, g_out, ws)
+
+
+def unet_grads(G, d_raw):
+    """vts_unet_grads over the modules' .grad tensors (allocated where missing)"""
+    g = L.UnetGrads()
+    g.d_raw, g.d_raw_nstride = d_raw.data_ptr(), d_raw.stride(0)
+    for i in range(G.num_downs):
+        names = [("down", "down%d" % i), ("up", "up%d" % i)] + ([("upT", "up%d_T" % i)] if i < G.num_layer_separate else [])
+        for field, name in names:
+            conv = getattr(G, name).conv
+            for p in (conv.weight, conv.bias):
+                if p is not None and p.grad is None:
+                    p.grad = torch.empty_like(p)
+            getattr(g, field + "_dw")[i] = conv.weight.grad.data_ptr()
+            getattr(g, field + "_db")[i] = L.ptr(conv.bias.grad if conv.bias is not None else None)
+    return g
+
+
+def unet_backward_c(G, ctx, d_raw, side_stream=None):
+    """the generator's backward through ONE C call (vts_unet_backward) on the workspace of unet_forward_train_c: overwrites every
+    parameter's .grad, bit-identical to unet_backward (tests/test_network_bwd_gpu.py)"""
+    lib = L.load()
+    x, style_tile, g_out, ws = ctx
+    d = unet_desc(G, x, g_out, style_tile, side_stream)
+    g = unet_grads(G, d_raw)
+    L.check(lib.vts_unet_backward(C.byref(d), C.byref(g), ws.data_ptr(), ws.numel(), L.stream()), "vts_unet_backward")
+
+
 def _style_map_forward(G, j, style, hh, ww):
     """style_code_mapping<j> (networks.py:1459-1465, 1611-1615): Linear(style_dim, P, bias=False) -> BatchNorm1d (batch_size > 1) |
     InstanceNorm1d -> ReLU, reshaped to [N, P / (h w), h, w].  The Linear is a 1 x 1 convolution on a 1 x 1 map; BatchNorm1d over
@@ -1271,6 +1314,65 @@ def _msd_scale_backward(D, s, a0, a1, acts, g, param_grads, accumulate, want_inp
             ops.conv4x4(Act(g), conv.weight.view(-1)[c0 * 16:], 16, cin * 16, c1, tgt, stride=st, pad=2, transposed=True, accumulate=acc_in)
             return tgt
     return None
+
+
+def msd_forward_train_c(D, in0, in1=None):
+    """the multiscale discriminator's training-mode forward through ONE vts_msd_forward call into a workspace sized for vts_msd_backward
+    (include/vts.h: the forward's region is its prefix).  in0 (++ in1): plain tensors.  Returns (preds, ctx) for msd_backward_c.  Not the
+    product's path (the training step keeps the Python schedule)."""
+    lib = L.load()
+    n, _, h, w = in0.shape
+    d = L.MsdDesc()
+    d.num_D = D.num_D
+    preds = []
+    hs, ws_ = h, w
+    for s in range(D.num_D):
+        ph, pw = hs, ws_
+        for ci in D.CONV_IDX:
+            ph, pw = ph // D.STRIDE[ci] + 1, pw // D.STRIDE[ci] + 1
+        pred = _empty(n, 1, ph, pw, in0.device)
+        sub, _, _ = patchgan_desc(D, s, in0, in1, pred=pred)      # (scale s's weights; the call fills in the pooled inputs and sizes)
+        d.scale[s] = sub
+        preds.append(pred)
+        hs, ws_ = (hs + 1) // 2, (ws_ + 1) // 2
+    need = int(lib.vts_msd_backward_ws_floats(C.byref(d)))
+    if need < 0:
+        raise RuntimeError("vts_msd_backward_ws_floats: %s" % lib.vts_last_error().decode())
+    ws = torch.empty(need, dtype=torch.float32, device=in0.device)
+    L.check(lib.vts_msd_forward(C.byref(d), ws.data_ptr(), ws.numel(), L.stream()), "vts_msd_forward")
+    return preds, (d, ws)
+
+
+def msd_grads(D, dpreds, param_grads=True, accumulate=False, input_grad=None):
+    """vts_msd_grads over the modules' .grad tensors (allocated where missing); arguments as msd_backward"""
+    g = L.MsdGrads()
+    for s in range(D.num_D):
+        layer = getattr(D, "layer%d" % (D.num_D - 1 - s))
+        sg = g.scale[s]
+        sg.dpred, sg.accumulate = dpreds[s].data_ptr(), int(accumulate)
+        if not param_grads:
+            continue
+        for j, ci in enumerate(D.CONV_IDX):
+            mods = [("dw", "db", getattr(layer, str(ci)))]
+            if ci in D.BN_IDX:
+                mods.append(("dgamma", "dbeta", getattr(layer, str(D.BN_IDX[ci]))))
+            for fw, fb, m in mods:
+                for p in (m.weight, m.bias):
+                    if p is not None and p.grad is None:
+                        p.grad = torch.zeros_like(p)
+                getattr(sg, fw)[j] = m.weight.grad.data_ptr()
+                getattr(sg, fb)[j] = L.ptr(m.bias.grad if m.bias is not None else None)
+    if input_grad is not None:
+        g.d_in, g.d_in_accumulate = input_grad[0].data_ptr(), int(bool(input_grad[1]))
+    return g
+
+
+def msd_backward_c(D, ctx, dpreds, param_grads=True, accumulate=False, input_grad=None):
+    """the multiscale discriminator's backward through ONE vts_msd_backward call on the workspace of msd_forward_train_c; arguments and
+    results as msd_backward (bit-identical to it: tests/test_network_bwd_gpu.py).  The running statistics are not touched."""
+    d, ws = ctx
+    g = msd_grads(D, dpreds, param_grads, accumulate, input_grad)
+    L.check(L.load().vts_msd_backward(C.byref(d), C.byref(g), ws.data_ptr(), ws.numel(), L.stream()), "vts_msd_backward")
 
 
 def _merge_input_grads(din_scales, input_grad, defer_last=False):

@@ -82,6 +82,16 @@ class UnetDesc(C.Structure):
     ]
 
 
+class UnetGrads(C.Structure):
+    """vts_unet_grads (include/vts.h): d_raw and the parameter gradients vts_unet_backward overwrites"""
+    _fields_ = [
+        ("d_raw", C.c_void_p), ("d_raw_nstride", C.c_int64),
+        ("down_dw", C.c_void_p * UNET_MAX_DOWNS), ("down_db", C.c_void_p * UNET_MAX_DOWNS),
+        ("up_dw", C.c_void_p * UNET_MAX_DOWNS), ("up_db", C.c_void_p * UNET_MAX_DOWNS),
+        ("upT_dw", C.c_void_p * UNET_MAX_DOWNS), ("upT_db", C.c_void_p * UNET_MAX_DOWNS),
+    ]
+
+
 PATCHGAN_MAX_CONVS, MSD_MAX_SCALES = 8, 4
 
 
@@ -102,6 +112,19 @@ class PatchganDesc(C.Structure):
 class MsdDesc(C.Structure):
     """vts_msd_desc: the multiscale discriminator's training-mode forward as one C call"""
     _fields_ = [("num_D", C.c_int), ("scale", PatchganDesc * MSD_MAX_SCALES)]
+
+
+class PatchganGrads(C.Structure):
+    """vts_patchgan_grads (include/vts.h): the gradients vts_patchgan_backward / vts_msd_backward write per scale"""
+    _fields_ = [
+        ("dpred", C.c_void_p), ("dw", C.c_void_p * PATCHGAN_MAX_CONVS), ("db", C.c_void_p * PATCHGAN_MAX_CONVS),
+        ("dgamma", C.c_void_p * PATCHGAN_MAX_CONVS), ("dbeta", C.c_void_p * PATCHGAN_MAX_CONVS), ("accumulate", C.c_int),
+        ("d_in", C.c_void_p), ("d_in_accumulate", C.c_int),
+    ]
+
+
+class MsdGrads(C.Structure):
+    _fields_ = [("scale", PatchganGrads * MSD_MAX_SCALES), ("d_in", C.c_void_p), ("d_in_accumulate", C.c_int)]
 
 
 class PatchJob(C.Structure):
@@ -132,7 +155,7 @@ SYMBOLS = [
     "vts_mask_select", "vts_mask_sample_ranks", "vts_adam_flat", "vts_adam_flat_dev", "vts_patchnce", "vts_l2norm_rows", "vts_patch_sample", "vts_linear_rows", "vts_copy_words",
     "vts_maxpool2_relu_pad", "vts_maxpool3s2_relu_pad", "vts_s2d4_pad", "vts_maxpool2_relu_bwd", "vts_relu_mask_pad", "vts_lpips_layer", "vts_l1_relu", "vts_lpips_input", "vts_lpips_input_bwd",
     "vts_patch_jobs", "vts_g_post_stack", "vts_step_begin", "vts_conv4x4_bsums", "vts_norm_bwd_from_partials",
-    "vts_u8_expand", "vts_unet_forward", "vts_unet_forward_ws_floats", "vts_patchgan_forward", "vts_patchgan_forward_ws_floats", "vts_msd_forward", "vts_msd_forward_ws_floats", "vts_allreduce_slice_plan", "vts_comm_unique_id", "vts_comm_init", "vts_allreduce_flat_async", "vts_allreduce_flat_wait", "vts_comm_destroy",
+    "vts_u8_expand", "vts_unet_forward", "vts_unet_forward_ws_floats", "vts_patchgan_forward", "vts_patchgan_forward_ws_floats", "vts_msd_forward", "vts_msd_forward_ws_floats", "vts_unet_backward", "vts_unet_backward_ws_floats", "vts_patchgan_backward", "vts_patchgan_backward_ws_floats", "vts_msd_backward", "vts_msd_backward_ws_floats", "vts_allreduce_slice_plan", "vts_comm_unique_id", "vts_comm_init", "vts_allreduce_flat_async", "vts_allreduce_flat_wait", "vts_comm_destroy",
 ]
 
 
@@ -170,6 +193,12 @@ def load():
     lib.vts_w3x3_wino_floats.argtypes = [C.c_int, C.c_int]
     lib.vts_w3x3_wino_floats.restype = C.c_int64
     lib.vts_unet_forward_ws_floats.restype = C.c_int64
+    lib.vts_unet_backward_ws_floats.argtypes = [C.POINTER(UnetDesc)]
+    lib.vts_unet_backward_ws_floats.restype = C.c_int64
+    lib.vts_patchgan_backward_ws_floats.argtypes = [C.POINTER(PatchganDesc)]
+    lib.vts_patchgan_backward_ws_floats.restype = C.c_int64
+    lib.vts_msd_backward_ws_floats.argtypes = [C.POINTER(MsdDesc)]
+    lib.vts_msd_backward_ws_floats.restype = C.c_int64
     lib.vts_patchgan_forward_ws_floats.argtypes = [C.POINTER(PatchganDesc)]
     lib.vts_patchgan_forward_ws_floats.restype = C.c_int64
     lib.vts_msd_forward_ws_floats.argtypes = [C.POINTER(MsdDesc)]
@@ -262,7 +291,9 @@ def load():
         "vts_conv3x3_wino": [vp, vp, vp, vp, i, i, i, i, i, i, i, vp, vp, vp],
         "vts_zero_border": [vp, i64, i, i, i, vp],
         "vts_maxpool3s2_relu_pad": [vp, i, i, i, i, vp, vp],
-        "vts_u8_expand": [vp, i64, i, vp, vp], "vts_unet_forward": [C.POINTER(UnetDesc), vp, i64, vp], "vts_patchgan_forward": [C.POINTER(PatchganDesc), vp, i64, vp], "vts_msd_forward": [C.POINTER(MsdDesc), vp, i64, vp], "vts_comm_unique_id": [vp], "vts_comm_init": [vp, i, i, vp], "vts_allreduce_flat_async": [vp, vp, i64, vp],
+        "vts_u8_expand": [vp, i64, i, vp, vp], "vts_unet_forward": [C.POINTER(UnetDesc), vp, i64, vp], "vts_unet_backward": [C.POINTER(UnetDesc), C.POINTER(UnetGrads), vp, i64, vp],
+        "vts_patchgan_backward": [C.POINTER(PatchganDesc), C.POINTER(PatchganGrads), vp, i64, vp],
+        "vts_msd_backward": [C.POINTER(MsdDesc), C.POINTER(MsdGrads), vp, i64, vp], "vts_patchgan_forward": [C.POINTER(PatchganDesc), vp, i64, vp], "vts_msd_forward": [C.POINTER(MsdDesc), vp, i64, vp], "vts_comm_unique_id": [vp], "vts_comm_init": [vp, i, i, vp], "vts_allreduce_flat_async": [vp, vp, i64, vp],
         "vts_allreduce_flat_wait": [vp, vp], "vts_comm_destroy": [vp], "vts_allreduce_slice_plan": [i64, i, i, vp, vp, vp, vp],
         "vts_s2d4_pad": [vp, i, i, i, i, i, i, i, vp, vp],
         "vts_maxpool2_relu_bwd": [vp, vp, i, i, i, vp, i, vp, i, vp],

@@ -397,6 +397,29 @@ int vts_bias_act_bwd(const float* g, const float* x, const float* bias, int N, i
                      void* stream);
 int vts_modconv_demod(const float* w, const float* s, int N, int Cout, int Cin, int KK, float scale, float eps, float* demod,
                       void* stream);
+/* Backward of ModulatedConv2d with a style vector, y = conv(x c s[n,ci], W) d[n,co] on the shared weight W, c = 1 / sqrt(Ci K^2)
+ * (the convolutions and their weight gradient run on vts_conv4x4 / vts_wgrad4x4 with c s and d as operand affines; these entries are the
+ * reductions and the demodulation's derivative that the style brings in).  All sums are combined in a fixed order: no atomics, results
+ * are bitwise repeatable.  Everything runs on `stream`; nothing is allocated and the host is never synchronised.
+ * vts_modconv_scale_dot   one pass over two maps a, b [NC, HW] (the (n, c) planes of NCHW tensors) with a per-plane factor f [NC]:
+ *                    out[nc, i] = a[nc, i] f[nc] when out != NULL (f may be NULL otherwise), and dot[nc] (+)= alpha sum_i a[nc, i] b[nc, i]
+ *                    (accumulate != 0 adds to dot).  (du, x, c s) -> dx and the convolution's share of ds; (g, y) without out -> sum g y
+ *                    = dd d.  Each of a, b is read once and out written once.  Planes of more than 1024 elements are cut into chunks
+ *                    whose partial sums go through `ws` (vts_modconv_scale_dot_ws_floats(NC, HW) floats, 0 for short planes: ws may
+ *                    then be NULL).  16-byte accesses when HW % 4 == 0 and a, b, out are 16-byte aligned, scalar ones otherwise.
+ * vts_modconv_demod_bwd   the demodulation d[n,co] = rsqrt(scale^2 sum_{ci,k} (w[co,ci,k] s[n,ci])^2 + eps) differentiated: from
+ *                    dd = dL/dd [N, Cout], d [N, Cout] (vts_modconv_demod), w [Cout, Cin, KK], s [N, Cin], with q = dd (-1/2) d^3:
+ *                    dw[co,ci,k] (+)= 2 scale^2 w[co,ci,k] sum_n q[n,co] s[n,ci]^2   and
+ *                    ds[n,ci]    (+)= 2 scale^2 s[n,ci] sum_co q[n,co] sum_k w[co,ci,k]^2     (KK <= 256, N <= 65535).
+ * vts_modconv_transpose   out[ci,co,k] (+)= w[co,ci,k]: the shared weight in the [Cin, Cout, KK] order of the stride-2 convolution whose
+ *                    input adjoint is the upsampling transposed convolution :320-330; called with (Cin, Cout) swapped and accumulate
+ *                    it folds that convolution's weight gradient back into dL/dW. */
+int64_t vts_modconv_scale_dot_ws_floats(int NC, int64_t HW);
+int vts_modconv_scale_dot(const float* a, const float* b, const float* f, int NC, int64_t HW, float alpha, float* out, float* dot,
+                          int accumulate, float* ws, int64_t ws_floats, void* stream);
+int vts_modconv_demod_bwd(const float* dd, const float* d, const float* w, const float* s, int N, int Cout, int Cin, int KK, float scale,
+                          float* dw, int accumulate_dw, float* ds, int accumulate_ds, void* stream);
+int vts_modconv_transpose(const float* w, int Cout, int Cin, int KK, float* out, int accumulate, void* stream);
 /* Style-free ModulatedConv2d weight of the StyleGAN2 generator's StyledConv layers (style = None -> s = 1, stylegan_networks.py:307-317,
  * 399-407): wout[co,ci,k] = v d[co], v = scale w, d[co] = rsqrt(sum_{ci,k} v^2 + eps); transpose != 0 stores [Ci,Co,KK] (the weight of
  * the stride-2 convolution whose input adjoint is the upsampling transposed convolution :320-330).  _bwd: dw (+)= scale (d g - d^3 v sum(g v))

@@ -118,6 +118,71 @@ class StyledConvUp(nn.Module):
         self.activate.bias = nn.Parameter(torch.zeros(1, cout, 1, 1))
 
 
+# ---- the style-conditioned blocks (stylegan_networks.py:248-437): parameter containers with the reference's constructor arguments and
+# state-dict keys; arithmetic in vts/engine.py (modulated_conv2d_forward / _backward, styled_conv_*, to_rgb_*).
+class ModulatedConv2d(nn.Module):
+    """:248-348 -- weight [1, Co, Ci, K, K], modulation = EqualLinear(style_dim, Ci, bias_init=1), blur.kernel when resampling"""
+
+    def __init__(self, in_channel, out_channel, kernel_size, style_dim, demodulate=True, upsample=False, downsample=False,
+                 blur_kernel=BLUR_TAPS):
+        super().__init__()
+        assert tuple(float(v) for v in blur_kernel) == BLUR_TAPS, "the engine's Blur passes use the (1, 3, 3, 1) kernel"
+        self.in_channel, self.out_channel, self.kernel_size = in_channel, out_channel, kernel_size
+        self.demodulate, self.upsample, self.downsample = demodulate, upsample, downsample
+        if upsample or downsample:
+            self.blur = _Holder()
+            self.blur.register_buffer("kernel", make_kernel(blur_kernel) * (4 if upsample else 1))
+        self.weight = nn.Parameter(torch.randn(1, out_channel, in_channel, kernel_size, kernel_size))
+        if style_dim is not None and style_dim > 0:
+            self.modulation = _Linear(style_dim, in_channel)
+            with torch.no_grad():
+                self.modulation.bias.fill_(1.0)
+
+    def forward(self, x, style):
+        from vts import engine
+        return engine.modulated_conv2d(x, style, self.weight, self.modulation.weight, self.modulation.bias, demodulate=self.demodulate,
+                                       upsample=self.upsample, downsample=self.downsample)
+
+
+class StyledConv(nn.Module):
+    """:378-415 -- ModulatedConv2d (plain or upsampling) -> NoiseInjection -> FusedLeakyReLU, called with a style vector"""
+
+    def __init__(self, in_channel, out_channel, kernel_size, style_dim=None, upsample=False, blur_kernel=BLUR_TAPS, demodulate=True,
+                 inject_noise=True):
+        super().__init__()
+        self.inject_noise = inject_noise
+        self.conv = ModulatedConv2d(in_channel, out_channel, kernel_size, style_dim, upsample=upsample, blur_kernel=blur_kernel,
+                                    demodulate=demodulate)
+        self.noise = _Holder()
+        self.noise.weight = nn.Parameter(torch.zeros(1))
+        self.activate = _Holder()
+        self.activate.bias = nn.Parameter(torch.zeros(1, out_channel, 1, 1))
+
+    def forward(self, x, style, noise=None):
+        from vts import engine
+        return engine.styled_conv_forward(self, x, style, noise)[0]
+
+
+class ToRGB(nn.Module):
+    """:418-437 -- 1 x 1 ModulatedConv2d without demodulation + bias (+ Upsample(blur_kernel) :98-116 of the skip image)"""
+
+    def __init__(self, in_channel, style_dim, upsample=True, blur_kernel=BLUR_TAPS):
+        super().__init__()
+        self.has_upsample = upsample
+        if upsample:
+            assert tuple(float(v) for v in blur_kernel) == BLUR_TAPS, "the engine's Upsample pass uses the (1, 3, 3, 1) kernel"
+            self.upsample = _Holder()
+            self.upsample.register_buffer("kernel", make_kernel(blur_kernel) * 4)
+            p = len(blur_kernel) - 2
+            self.up_pad = ((p + 1) // 2 + 1, p // 2)
+        self.conv = ModulatedConv2d(in_channel, 3, 1, style_dim, demodulate=False)
+        self.bias = nn.Parameter(torch.zeros(1, 3, 1, 1))
+
+    def forward(self, x, style, skip=None):
+        from vts import engine
+        return engine.to_rgb_forward(self, x, style, skip)[0]
+
+
 def g_channels(ngf):
     """stylegan_networks.py:805-816"""
     m = ngf / 32

@@ -1935,33 +1935,196 @@ def sg2d_backward(D, ctx, dout, accumulate=False, input_grad=False, param_grads=
     return _sg_layer_backward(D.convs[0], ctx.x_shape, ctx.first, g, SQRT2, accumulate, want_dx=input_grad, param_grads=pg)
 
 
-def modulated_conv2d(x, style, weight, mod_weight, mod_bias, demodulate=True, downsample=False):
-    """ModulatedConv2d.forward (:304-348), forward only, for the plain and the downsampling form (the upsampling form -- a
-    transposed convolution followed by Blur -- is not built).  Instead of the reference's per-sample weights in a grouped
-    convolution: y = conv(x * s[n,ci] / sqrt(fan_in), W) * demod[n,co] on the shared weight W = weight[0]; both factors ride on the
-    operand affines.  style [N, style_dim]; the modulation is EqualLinear(style_dim, Ci, bias_init=1) (:199-227)."""
+_SG_BUF = {}
+
+
+def _sg_buf(tag, like, shape):
+    """persistent scratch tied to a parameter (its address is stable, so captured graphs keep pointing at the same buffer)"""
+    key = (tag, like.data_ptr(), tuple(shape))
+    t = _SG_BUF.get(key)
+    if t is None:
+        t = _SG_BUF[key] = torch.empty(shape, dtype=torch.float32, device=like.device)
+    return t
+
+
+def _k4():
     from models.stylegan2_blocks import BLUR_KERNEL
+    return [[4.0 * v for v in row] for row in BLUR_KERNEL]
+
+
+class ModConvCtx:
+    """what modulated_conv2d_backward needs: the input, the style, s = modulation(style), the operand scale c * s, the demodulation
+    coefficients d (None without demodulation), the output y, the blurred operand (downsampling form), the weight views"""
+    __slots__ = ("form", "x", "style", "s", "cs", "d", "y", "tb", "wt", "wT", "mod_weight", "scale", "k", "pads")
+
+
+def modulated_conv2d_forward(x, style, weight, mod_weight, mod_bias, demodulate=True, upsample=False, downsample=False, keep=True):
+    """ModulatedConv2d.forward (:304-348) with a style vector, all four forms.  Instead of the reference's per-sample weights in a
+    grouped convolution: y = conv(x * s[n,ci] / sqrt(fan_in), W) * demod[n,co] on the shared weight W = weight[0]; both factors ride on
+    the operand affines.  style [N, style_dim]; the modulation is EqualLinear(style_dim, Ci, bias_init=1) (:199-227), a 1 x 1 convk.
+    plain: pad K // 2.  downsample: Blur (:277-283), then stride 2.  upsample: the transposed stride-2 convolution (:320-330) is the input
+    adjoint of the stride-2 K x K convolution on the weight in [Ci, Co, K, K] order, then demod, then Blur with the 4x kernel (:269-275).
+    Returns (y, ctx); ctx is None unless keep."""
+    from models.stylegan2_blocks import BLUR_KERNEL
+    assert not (upsample and downsample)
     n, ci, h, w_ = x.shape
     wt = weight.view(weight.shape[-4], ci, weight.shape[-2], weight.shape[-1])
     co, k = wt.shape[0], wt.shape[2]
     sd = style.shape[1]
+    st4 = style.reshape(n, sd, 1, 1).contiguous()
     s = _empty(n, ci, 1, 1, x.device)
-    ops.convk(_scaled(style.reshape(n, sd, 1, 1).contiguous(), 1.0 / sd ** 0.5), mod_weight.view(ci, sd, 1, 1), s, bias=mod_bias, pad=0)
+    ops.convk(_scaled(st4, 1.0 / sd ** 0.5), mod_weight.view(ci, sd, 1, 1), s, bias=mod_bias, pad=0)
     scale = 1.0 / (ci * k * k) ** 0.5
-    xin = Act(x, (s.view(-1) * scale).contiguous(), _const(n * ci, 0.0, x.device))
-    if downsample:
+    cs = (s.view(-1) * scale).contiguous()
+    xin = Act(x, cs, _const(n * ci, 0.0, x.device))
+    demod = ops.modconv_demod(wt, s.view(n, ci), scale) if demodulate else None
+    tb = wT = pads = None
+    if upsample:
+        p = 2 - (k - 1)
+        pads = ((p + 1) // 2 + 1, p // 2 + 1)
+        wT = ops.modconv_transpose(wt, _sg_buf("modconv_wT", weight, (ci, co, k, k)))
+        pre = _empty(n, co, 2 * (h - 1) + k, 2 * (w_ - 1) + k, x.device)
+        ops.convk_s2_bwd_data(xin, wT, pre)
+        out = ops.upfirdn2d(pre, _k4(), pad=pads)                      # d[n,co] is per channel: it commutes with the Blur
+    elif downsample:
         p = 2 + (k - 1)
+        pads = ((p + 1) // 2, p // 2)
         t = ops.pad_affine(xin, (0, 0, 0, 0), 0)                      # materialise x * s, then Blur (:323-327), then stride 2
-        t = ops.upfirdn2d(t, BLUR_KERNEL, pad=((p + 1) // 2, p // 2))
-        out = _empty(n, co, (t.shape[2] - k) // 2 + 1, (t.shape[3] - k) // 2 + 1, x.device)
-        ops.convk_s2(t, wt, out)
+        tb = ops.upfirdn2d(t, BLUR_KERNEL, pad=pads)
+        out = _empty(n, co, (tb.shape[2] - k) // 2 + 1, (tb.shape[3] - k) // 2 + 1, x.device)
+        ops.convk_s2(tb, wt, out)
     else:
         out = _empty(n, co, h, w_, x.device)
         ops.convk(xin, wt, out, pad=k // 2)
-    if not demodulate:
-        return out
-    demod = ops.modconv_demod(wt, s.view(n, ci), scale)
-    return ops.pad_affine(Act(out, demod.view(-1), _const(n * co, 0.0, x.device)), (0, 0, 0, 0), 0)
+    y = out if demod is None else ops.pad_affine(Act(out, demod.view(-1), _const(n * co, 0.0, x.device)), (0, 0, 0, 0), 0)
+    if not keep:
+        return y, None
+    ctx = ModConvCtx()
+    ctx.form = "up" if upsample else ("down" if downsample else "plain")
+    ctx.x, ctx.style, ctx.s, ctx.cs, ctx.d, ctx.y, ctx.tb, ctx.wt, ctx.wT = x, st4, s, cs, demod, y, tb, wt, wT
+    ctx.mod_weight, ctx.scale, ctx.k, ctx.pads = mod_weight, scale, k, pads
+    return y, ctx
+
+
+def modulated_conv2d(x, style, weight, mod_weight, mod_bias, demodulate=True, downsample=False, upsample=False):
+    """ModulatedConv2d.forward (:304-348) without a context: modulated_conv2d_forward(...)[0]"""
+    return modulated_conv2d_forward(x, style, weight, mod_weight, mod_bias, demodulate=demodulate, upsample=upsample, downsample=downsample,
+                                    keep=False)[0]
+
+
+def modulated_conv2d_backward(ctx, g, *, dweight, dmod_weight, dmod_bias, accumulate=False, want_dx=True, want_dstyle=True):
+    """backward of modulated_conv2d_forward for g = dL/dy: the parameter gradients are written into (accumulate: added to) dweight
+    [1,Co,Ci,K,K], dmod_weight [Ci, style_dim], dmod_bias [Ci]; returns (dx or None, dstyle [N, style_dim] or None).
+    With u = x c s, z = conv(u, W), y = z d:  dz = g d (an operand affine), dd = sum_hw g y / d, du = conv^T(dz, W), dx = du c s,
+    ds = c sum_hw du x + the demodulation's share (vts_modconv_demod_bwd), dW = wgrad(u, dz) + the demodulation's share; the
+    modulation layer's backward runs on the 1 x 1 members of the convolution family like its forward.  No atomics anywhere: two calls
+    give the same bits."""
+    from models.stylegan2_blocks import BLUR_KERNEL
+    x, wt, k, scale = ctx.x, ctx.wt, ctx.k, ctx.scale
+    n, ci, h, w_ = x.shape
+    co, dev = wt.shape[0], x.device
+    g = g.contiguous()
+    dw = dweight.view(co, ci, k, k)
+    xin = Act(x, ctx.cs, _const(n * ci, 0.0, dev))
+    du = _empty(n, ci, h, w_, dev)
+    if ctx.form == "up":
+        gb = _empty(n, co, 2 * (h - 1) + k, 2 * (w_ - 1) + k, dev)
+        ops.upfirdn2d_bwd(g, gb, _k4(), pad=ctx.pads)                  # Blur^T first, d afterwards (per channel: they commute)
+        dz = gb if ctx.d is None else Act(gb, ctx.d.view(-1), _const(n * co, 0.0, dev))
+        ops.convk_s2(dz, ctx.wT, du)
+        dwT = _sg_buf("modconv_dwT", dweight, (ci, co, k, k))
+        ops.wgradk_s2(xin, dz, dwT)                                    # weight gradient of the stride-2 convolution pairing (dz -> u)
+        ops.modconv_transpose(dwT, dw, accumulate=accumulate)
+    else:
+        dz = g if ctx.d is None else Act(g, ctx.d.view(-1), _const(n * co, 0.0, dev))
+        if ctx.form == "down":
+            dtb = torch.empty_like(ctx.tb)
+            ops.convk_s2_bwd_data(dz, wt, dtb)
+            ops.wgradk_s2(dz, ctx.tb, dw, accumulate=accumulate)
+            ops.upfirdn2d_bwd(dtb, du, BLUR_KERNEL, pad=ctx.pads)
+        else:
+            ops.convk_bwd_data(dz, wt, du, pad=k // 2)
+            ops.wgradk(dz, xin, dw, pad=k // 2, accumulate=accumulate)
+    ds = torch.empty(n, ci, dtype=torch.float32, device=dev)
+    dx = torch.empty_like(x) if want_dx else None
+    ops.modconv_scale_dot(du, x, ds, f=ctx.cs, out=dx, alpha=scale)    # dx = du c s  and  ds = c sum_hw du x  in one pass
+    if ctx.d is not None:
+        gy = torch.empty(n, co, dtype=torch.float32, device=dev)
+        ops.modconv_scale_dot(g, ctx.y, gy)                            # sum_hw g y = dd d  (y is what the forward keeps, d > 0)
+        ops.modconv_demod_bwd(gy / ctx.d, ctx.d, wt, ctx.s.view(n, ci), scale, dw, ds, accumulate_dw=True, accumulate_ds=True)
+    sd = ctx.style.shape[1]
+    ds4 = ds.view(n, ci, 1, 1)
+    mw = ctx.mod_weight.view(ci, sd, 1, 1)
+    ops.wgradk(ds4, _scaled(ctx.style, 1.0 / sd ** 0.5), dmod_weight.view(ci, sd, 1, 1), pad=0, accumulate=accumulate)
+    ops.channel_sum(ds4, dmod_bias, accumulate=accumulate)
+    dstyle = None
+    if want_dstyle:
+        dstyle = _empty(n, sd, 1, 1, dev)
+        ops.convk_bwd_data(_scaled(ds4, 1.0 / sd ** 0.5), mw, dstyle, pad=0)
+        dstyle = dstyle.view(n, sd)
+    return dx, dstyle
+
+
+def _grad(p):
+    if p.grad is None:
+        p.grad = torch.zeros_like(p)
+    return p.grad
+
+
+def styled_conv_forward(m, x, style, noise=None):
+    """StyledConv.forward with a style (:408-415; m: models.stylegan2_blocks.StyledConv): ModulatedConv2d plain or upsampling ->
+    NoiseInjection (:351-363; the reference draws fresh N(0, 1) noise when none is given -- the draw is an input here) -> FusedLeakyReLU.
+    Returns (y, saved)."""
+    c = m.conv
+    z, ctx = modulated_conv2d_forward(x, style, c.weight, c.modulation.weight, c.modulation.bias, demodulate=c.demodulate, upsample=c.upsample)
+    if m.inject_noise:
+        if noise is None:
+            noise = torch.randn(z.shape[0], 1, z.shape[2], z.shape[3], device=x.device)
+        z = ops.pad_affine(z, (0, 0, 0, 0), 0, res=(noise * m.noise.weight).expand(-1, z.shape[1], -1, -1).contiguous())
+    y = ops.bias_act(z, m.activate.bias, 0.2, SQRT2)
+    return y, (ctx, z, noise)
+
+
+def styled_conv_backward(m, saved, g, accumulate=False, want_dx=True, want_dstyle=True):
+    """parameter gradients into .grad (created when missing); returns (dx, dstyle)"""
+    ctx, z, noise = saved
+    c = m.conv
+    dz = ops.bias_act_bwd(g.contiguous(), z, m.activate.bias, 0.2, SQRT2)
+    ops.channel_sum(dz, _grad(m.activate.bias).view(-1), accumulate=accumulate)
+    if m.inject_noise:
+        gw = (dz.sum(1, keepdim=True) * noise).sum().view(1)           # one scalar parameter: d weight = <dz summed over channels, noise>
+        ng = _grad(m.noise.weight)
+        ng.copy_(ng + gw if accumulate else gw)
+    return modulated_conv2d_backward(ctx, dz, dweight=_grad(c.weight), dmod_weight=_grad(c.modulation.weight), dmod_bias=_grad(c.modulation.bias),
+                                     accumulate=accumulate, want_dx=want_dx, want_dstyle=want_dstyle)
+
+
+def to_rgb_forward(m, x, style, skip=None):
+    """ToRGB.forward (:428-437; m: models.stylegan2_blocks.ToRGB): 1 x 1 modulated convolution without demodulation + bias
+    (+ Upsample(blur_kernel) of the skip image, :98-116).  Returns (y, saved)."""
+    c = m.conv
+    z, ctx = modulated_conv2d_forward(x, style, c.weight, c.modulation.weight, c.modulation.bias, demodulate=False)
+    up = None
+    if skip is not None:
+        assert m.has_upsample, "ToRGB(upsample=False) takes no skip image"
+        up = ops.upfirdn2d(skip, _k4(), up=2, down=1, pad=m.up_pad)
+    y = ops.bias_act(z, m.bias, 1.0, 1.0, res=up)                      # slope 1, gain 1: z + bias (+ upsampled skip)
+    return y, (ctx, None if skip is None else tuple(skip.shape))
+
+
+def to_rgb_backward(m, saved, g, accumulate=False, want_dx=True, want_dstyle=True):
+    """parameter gradients into .grad (created when missing); returns (dx, dstyle, dskip or None)"""
+    ctx, skip_shape = saved
+    c = m.conv
+    g = g.contiguous()
+    ops.channel_sum(g, _grad(m.bias).view(-1), accumulate=accumulate)
+    dskip = None
+    if skip_shape is not None:
+        dskip = torch.empty(skip_shape, dtype=torch.float32, device=g.device)
+        ops.upfirdn2d_bwd(g, dskip, _k4(), up=2, down=1, pad=m.up_pad)
+    dx, dstyle = modulated_conv2d_backward(ctx, g, dweight=_grad(c.weight), dmod_weight=_grad(c.modulation.weight),
+                                           dmod_bias=_grad(c.modulation.bias), accumulate=accumulate, want_dx=want_dx, want_dstyle=want_dstyle)
+    return dx, dstyle, dskip
 
 
 # ---- generator side (`--netG stylegan2 | smallstylegan2`; reference stylegan_networks.py:800-930) ------------------------------------
@@ -1985,11 +2148,6 @@ def _sg_resblock_backward(blk, saved, g, accumulate, pg=True):
     else:
         dx = ops.pad_affine(_scaled(g, 1.0 / SQRT2), (0, 0, 0, 0), 0)
     return _sg_layer_backward(blk.conv1, x_shape, s1, dy1, SQRT2, accumulate, dx=dx, dx_accumulate=True, param_grads=pg)
-
-
-def _k4():
-    from models.stylegan2_blocks import BLUR_KERNEL
-    return [[4.0 * v for v in row] for row in BLUR_KERNEL]
 
 
 def _styled_up_forward(m, x, noise=None):

@@ -674,6 +674,43 @@ def modconv_demod(w, s, scale, eps=1e-8):
     return out
 
 
+def modconv_scale_dot(a, b, dot, f=None, out=None, alpha=1.0, accumulate=False):
+    """One pass over the NCHW maps a, b: out = a * f[n, c] (when `out` is given) and dot[n, c] (+)= alpha * sum_hw a * b (include/vts.h).
+    f, dot: N * C floats.  Returns dot."""
+    n, c = a.shape[0], a.shape[1]
+    hw = a.numel() // (n * c)
+    assert a.shape == b.shape and a.is_contiguous() and b.is_contiguous() and dot.is_contiguous() and dot.numel() == n * c
+    assert out is None or (f is not None and out.shape == a.shape and out.is_contiguous() and f.is_contiguous() and f.numel() == n * c)
+    lib = L.load()
+    need = lib.vts_modconv_scale_dot_ws_floats(n * c, hw)
+    ws = workspace(need, a.device) if need else None
+    _run("modconv_scale_dot", 4.0 * a.numel() * (3 if out is not None else 2), 2.0 * a.numel(), lib.vts_modconv_scale_dot, a.data_ptr(),
+         b.data_ptr(), L.ptr(f), n * c, hw, alpha, L.ptr(out), dot.data_ptr(), int(accumulate), L.ptr(ws), ws.numel() if need else 0, L.stream())
+    return dot
+
+
+def modconv_demod_bwd(dd, d, w, s, scale, dw, ds, accumulate_dw=False, accumulate_ds=False):
+    """demodulation share of the ModulatedConv2d backward (include/vts.h): dd = dL/d(demod) [N, Co], d = modconv_demod(w, s, scale),
+    w [Co,Ci,K,K] (or [1,Co,Ci,K,K]), s [N, Ci]; dw (+)= ..., ds (+)= ..."""
+    co, ci, kk = w.shape[-4], w.shape[-3], w.shape[-1] * w.shape[-2]
+    n = s.shape[0]
+    assert dd.numel() == d.numel() == n * co and s.numel() == ds.numel() == n * ci and dw.numel() == w.numel()
+    assert all(t.is_contiguous() for t in (dd, d, w, s, dw, ds))
+    _run("modconv_demod_bwd", 4.0 * ((n + 2 + int(accumulate_dw)) * w.numel()), 5.0 * n * w.numel(), L.load().vts_modconv_demod_bwd, dd.data_ptr(),
+         d.data_ptr(), w.data_ptr(), s.data_ptr(), n, co, ci, kk, scale, dw.data_ptr(), int(accumulate_dw), ds.data_ptr(), int(accumulate_ds),
+         L.stream())
+    return dw, ds
+
+
+def modconv_transpose(w, out, accumulate=False):
+    """out [B,A,K,K] (+)= w [A,B,K,K] with the two channel axes swapped (include/vts.h)"""
+    a, b, kk = w.shape[-4], w.shape[-3], w.shape[-1] * w.shape[-2]
+    assert w.is_contiguous() and out.is_contiguous() and out.numel() == w.numel()
+    _run("modconv_transpose", 4.0 * w.numel() * (3 if accumulate else 2), 0.0, L.load().vts_modconv_transpose, w.data_ptr(), a, b, kk,
+         out.data_ptr(), int(accumulate), L.stream())
+    return out
+
+
 def w3x3_pack(w, mode, tag=None):
     """tap-major packing of a 3x3 weight for the *_wide kernels into a persistent buffer (see include/vts.h).
     w is an nn.Conv2d weight [Co,Ci,3,3] for the conv_* modes, an nn.ConvTranspose2d weight [Ci,Co,3,3] for convT_*."""

@@ -5,8 +5,6 @@ run() { echo "== $*" >> $O; env "$@" python bench.py --steps 150 --warmup 10 --n
 run A=1
 run VTS_WGRAD_NS_WGS=256
 run VTS_WGRAD_NS_WGS=384
-run VTS_WGRAD_FLUSH_MB=32
-run VTS_WGRAD_FLUSH_MB=512
 run VTS_WGRAD_CAP_MB=4
 run VTS_FUSE_STATS=0
 run A=2

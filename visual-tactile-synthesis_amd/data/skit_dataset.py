@@ -21,7 +21,6 @@ Not kept (continued):
 """
 import ntpath
 import os
-from vts import tune
 import time
 
 import numpy as np
@@ -150,10 +149,9 @@ class SkitDataset(SingleSkitDataset):
                 d.update({"M": M_tensor, "M_paths": self.M_paths[mi]})
             if self.style_codes[mi] is not None:
                 d["style_code"] = torch.from_numpy(self.style_codes[mi])
-            if tune.get("VTS_U8_BATCH", "1") != "0":      # (not a reference key: singleskit_dataset.to_u8)
-                for key, pic in (("S", S3), ("I", I3), ("M", M3)):
-                    raw = to_u8(pic) if key in d else None
-                    if raw is not None and tuple(raw.shape) == tuple(d[key].shape):
-                        d[key + "_u8"] = raw
+            for key, pic in (("S", S3), ("I", I3), ("M", M3)):      # (not reference keys: singleskit_dataset.to_u8)
+                raw = to_u8(pic) if key in d else None
+                if raw is not None and tuple(raw.shape) == tuple(d[key].shape):
+                    d[key + "_u8"] = raw
             self.data_dict[index] = d
         print("Finish preprocessing %d data, takes " % len(self), time.time() - t0)

@@ -31,14 +31,6 @@ from vts.optim import FlatAdam, FlatParams
 from . import networks
 from .base_model import BaseModel
 
-# 1 (default): on one GPU the generator's discriminator-free loss terms run as one more lane beside the discriminator updates; 0: serially
-# behind them (A/B timing; results are identical: the lanes only read the forward's outputs and add into their own fixed-point loss slots)
-G_PRE_LANE = tune.get("VTS_G_PRE_LANE", "1") != "0"
-D2_TAIL_LANE = tune.get("VTS_D2_TAIL_LANE", "1") != "0"    # joined / data-parallel schedule: D2's generator-step forward as a lane under the backward
-FUSE_MERGE = tune.get("VTS_FUSE_MERGE", "1") != "0"       # last level of the D1 input-gradient pyramid merge inside g_out_grad
-D2_CHAIN = tune.get("VTS_D2_CHAIN", "lanes")      # "serial": the whole D2 chain as one lane (measurement: see _run_d_chains)
-D1_REAL_EARLY = tune.get("VTS_D1_REAL_EARLY", "1") != "0"     # D1's pass on the real images beside the generator forward (see _seg_d_updates)
-
 B = str2bool
 
 # (flag, type, default[, choices])  -- reference: sinskitG_model.py:52-296
@@ -249,7 +241,7 @@ class SinSKITGModel(BaseModel):
         self._d2_lane = None
         self._infer_graph, self._infer_eager_done = None, False   # captured inference forward (test())
         self._eager_steps_done = 0
-        if tune.get("VTS_KO_LANES", None) and tune.get("VTS_KO_LANES_ACK", "") != "timing-only":
+        if engine.KO_LANES and tune.get("VTS_KO_LANES_ACK", "") != "timing-only":
             raise RuntimeError("VTS_KO_LANES skips discriminator lanes (wrong losses and gradients): set VTS_KO_LANES_ACK=timing-only to run the timing experiment")
         self._draws = None      # tests / parity runs inject {"aug": [4,N], "more_idx": [N,K]}
         self.ddp = None
@@ -434,10 +426,7 @@ class SinSKITGModel(BaseModel):
             if self._stage_done[par] is not None:
                 cs.wait_event(self._stage_done[par])      # the device -> device copy that read this staging block two batches ago
             with torch.cuda.stream(cs):
-                if tune.get("VTS_PATCH_COPY_KERNEL", "0") == "1":
-                    L.check(L.load().vts_copy_words(pin.data_ptr(), stage.data_ptr(), words, L.stream()), "vts_copy_words")
-                else:   # a DMA copy: a kernel on a fifth stream waits for one of the four hardware queues the step's lanes occupy
-                    stage.copy_(pin, non_blocking=True)
+                stage.copy_(pin, non_blocking=True)      # a DMA copy: a kernel on a fifth stream waits for one of the four hardware queues the step's lanes occupy
                 self._pin_evt[tag].record(cs)
                 evt = torch.cuda.Event()
                 evt.record(cs)
@@ -457,10 +446,9 @@ class SinSKITGModel(BaseModel):
         self._stage_parity ^= 1
         # 8-bit sources (optional keys S_u8 / I_u8 / M_u8 next to the float tensors: the dataset front-ends attach them where the float
         # tensor IS ToTensor [+ Normalize] of those bytes): a quarter of the PCIe traffic, expanded on the device bit for bit (vts_u8_expand)
-        u8 = tune.get("VTS_U8_BATCH", "1") != "0"
 
         def image(key, normalize):
-            if u8 and (key + "_u8") in input:
+            if (key + "_u8") in input:
                 raw = self._load("%s_%s_u8" % (phase, key), input[key + "_u8"], dtype=torch.uint8, staged=True)
                 par = self._stage_parity
                 f = self._bufs.get("%s_%s_f%d" % (phase, key, par))
@@ -471,7 +459,7 @@ class SinSKITGModel(BaseModel):
 
         # the usual training batch (8-bit S / I / M, background mask, [fake | real] pair buffers): ONE launch writes M, both copies of the
         # masked sketch and the masked real image from the three staged byte tensors (vts_input_images_u8; seven launches otherwise)
-        fused = (u8 and tune.get("VTS_FUSED_INPUT", "1") != "0" and self.opt.use_bg_mask and self.isTrain and phase == "train"
+        fused = (tune.get("VTS_FUSED_INPUT", "1") != "0" and self.opt.use_bg_mask and self.isTrain and phase == "train"
                  and "I" in input and all((k + "_u8") in input for k in ("S", "I", "M")))
         if fused:
             rawS, rawI, rawM = (self._load("%s_%s_u8" % (phase, k), input[k + "_u8"], dtype=torch.uint8, staged=True) for k in ("S", "I", "M"))
@@ -550,7 +538,7 @@ class SinSKITGModel(BaseModel):
             if "val_T_images" in input and len(input["val_T_images"]) > 0:
                 # only compute_metrics reads the validation patches: in the training phase they are uploaded on first use (the `val_set`
                 # property) instead of with every batch -- a host staging copy, a DMA and two launches per step saved
-                if phase == "train" and tune.get("VTS_LAZY_VAL_SET", "1") != "0":
+                if phase == "train":
                     self._val_pending = (phase + "_va", input["val_T_images"], input["val_I_masks"], input["val_T_coords"])
                 else:
                     self.val_set = self._patch_set(phase + "_va", input["val_T_images"], input["val_I_masks"], input["val_T_coords"])
@@ -573,20 +561,15 @@ class SinSKITGModel(BaseModel):
             pin = self._bufs.get("cand_count_pin")
             if pin is None or pin.numel() != n:
                 pin = self._bufs["cand_count_pin"] = torch.empty(n, dtype=torch.int32).pin_memory()
-            if getattr(self, "_copy_stream", None) is not None and tune.get("VTS_CAND_COPY_STREAM", "1") != "0":
-                # off the launch stream: a device -> host copy between set_input's kernels and the step's graphs costs the launch stream two
-                # engine switches (~ 0.1 ms of idle device); nothing on the launch stream reads it
-                ready = torch.cuda.Event()
-                ready.record()
-                self._copy_stream.wait_event(ready)
-                with torch.cuda.stream(self._copy_stream):
-                    pin.copy_(self._cand_prefix[:, -1], non_blocking=True)
-                    evt = torch.cuda.Event()
-                    evt.record(self._copy_stream)
-            else:
+            # off the launch stream: a device -> host copy between set_input's kernels and the step's graphs costs the launch stream two
+            # engine switches (~ 0.1 ms of idle device); nothing on the launch stream reads it
+            ready = torch.cuda.Event()
+            ready.record()
+            self._copy_stream.wait_event(ready)
+            with torch.cuda.stream(self._copy_stream):
                 pin.copy_(self._cand_prefix[:, -1], non_blocking=True)
                 evt = torch.cuda.Event()
-                evt.record()
+                evt.record(self._copy_stream)
             self._cand_check = (pin, evt, k, self.name)
             self._ranks = self._buf("more_ranks", (n, k), torch.int64)
             mi = self._bufs.get("more_img")          # image index of every extra patch: a constant of (n, k), built on the device once
@@ -736,18 +719,14 @@ class SinSKITGModel(BaseModel):
         if not (self.opt.use_more_fakeT and "D2" in self.model_names):
             return
         k = self.opt.add_fake_T_sample_size
-        if self._draws is None and tune.get("VTS_HOST_RANKS", "0") != "1":
+        if self._draws is None:
             # drawn on the device (vts_mask_sample_ranks: Floyd's algorithm over the candidate count the device already holds, seeded from
             # Python's `random` so that random.seed() still fixes the run).  The host used to fetch that count first -- a second evaluation
             # of the candidate map on the copy stream, a pinned read-back and a spin on its event, ~5 ms per iteration with a fresh batch
             # (tools/prof_fresh.py) -- and to upload the ranks it drew.
             ops.mask_sample_ranks(self._cand_prefix, self.M.shape[2], k, random.getrandbits(64), self._ranks)
             return
-        if self._draws is not None:
-            ranks = torch.as_tensor(self._draws["more_idx"]).long()
-        else:
-            counts = self._cand_prefix[:, -1].tolist()       # (VTS_HOST_RANKS=1: the host-side draw of round 2, synchronising)
-            ranks = torch.tensor([random.sample(range(c), k) for c in counts], dtype=torch.int64)
+        ranks = torch.as_tensor(self._draws["more_idx"]).long()
         pin = self._bufs.get("ranks_pin")
         if pin is None or pin.shape != ranks.shape:
             pin = self._bufs["ranks_pin"] = torch.empty(ranks.shape, dtype=torch.int64).pin_memory()
@@ -816,9 +795,10 @@ class SinSKITGModel(BaseModel):
         # D1 on the REAL images does not depend on the generator: its three scales (forward, backward, weight gradients) run on side streams
         # BESIDE the generator forward, which is one chain that leaves most of the chip idle.  The pass only records its BatchNorm
         # statistics; the fake pass below splices the running-statistics update in behind its own (the reference's order: fake, then
-        # real, sinskitG_model.py:1361-1374) and accumulates its gradients onto these.  VTS_D1_REAL_EARLY=0: one batched [fake | real] pass.
+        # real, sinskitG_model.py:1361-1374) and accumulates its gradients onto these.  Where it cannot run early (the serial schedule,
+        # StyleGAN2-D, unpaired input): one batched [fake | real] pass, or two passes, below.
         p_real_early = None
-        if (D1_REAL_EARLY and "D" in self.model_names and self._pair and not getattr(self.netD, "is_stylegan2_d", False)
+        if ("D" in self.model_names and self._pair and not getattr(self.netD, "is_stylegan2_d", False)
                 and getattr(self, "_I2_pyr", None) is not None and engine.PARALLEL_SCALES):
             lam = opt.lambda_G1_GAN
             pyr = [self._d1_pair(Act(S[n:2 * n]), Act(I[n:2 * n])) for S, I in zip(self._S2_pyr, self._I2_pyr)]
@@ -827,7 +807,7 @@ class SinSKITGModel(BaseModel):
                                 stat_only=True, keep_stats=True)
             ops.step_begin(self._loss_buf, self._step_counters)      # (in front of the fork: the real pass adds into its loss slot)
             engine.msd_multi([(self.netD, [p_real_early])], self.criterionGAN, extra=lambda: self._forward_and_stacks(begin=False), extra_cost=1.0,
-                             extra_main=True, streams=int(tune.get("VTS_PHASE_A_STREAMS", "3")))
+                             extra_main=True, streams=3)      # the forward's launch stream + two for the real pass (2 / 4: + 0.20 / + 0.05 ms)
         else:
             self._forward_and_stacks()
         jobs = []
@@ -890,7 +870,7 @@ class SinSKITGModel(BaseModel):
         # D / D2 all-reduces travel under)
         self._g_pre_done = False
         extra = None
-        if G_PRE_LANE and not self._ddp_segments():
+        if not self._ddp_segments():
             def extra():
                 self._seg_g_pre()
                 self._g_pre_done = True
@@ -917,7 +897,7 @@ class SinSKITGModel(BaseModel):
         opt = self.opt
         heavy = opt.lambda_G1_lpips > 0.0 or opt.lambda_G2_lpips > 0.0
         nets = [getattr(self, "net" + n) for n in ("D", "D2") if n in self.model_names]
-        return bool(engine.D_CHAINS and G_PRE_LANE and not self._ddp_segments() and not heavy and nets
+        return bool(engine.D_CHAINS and not self._ddp_segments() and not heavy and nets
                     and not any(getattr(net, "is_stylegan2_d", False) for net in nets)
                     and isinstance(self.netG, networks.CustomUnetGenerator))
 
@@ -938,7 +918,7 @@ class SinSKITGModel(BaseModel):
                     in0, in1 = self._d1_pair(self.real_S, self.fake_I)
                     g = [dict(in0=in0, in1=in1, real=True, coeff=lam, slot=slot["G_GAN"], grad_coeff=lam, param_grads=False,
                               input_grad=(self._d_fake_I, self._have_dI), pyr=self._d1_pyramid(self.real_S.shape[0], pool_fake=False),
-                              defer_merge=FUSE_MERGE)]      # the last pool^T of the pyramid merge rides in g_out_grad (_g_backward)
+                              defer_merge=True)]      # the last pool^T of the pyramid merge rides in g_out_grad (_g_backward)
                     self._have_dI = True
                     self._g_gan_pass = g[0]
                     return g
@@ -951,15 +931,12 @@ class SinSKITGModel(BaseModel):
         self._d2_lane = None
         if chain_d2 is None or chain_d1 is None:
             engine.msd_chain(chain_d1 or chain_d2, self.criterionGAN, side=g_pre)
-        elif D2_CHAIN == "serial":
-            # measured (round 6): the whole D2 chain as ONE lane is ~2.5 ms of dependent small launches and becomes the step's critical
-            # path (6.00 against 5.41 ms)
-            self._d2_lane = engine.fork_lane(lambda: engine.msd_chain(chain_d2, self.criterionGAN, serial=True))
-            engine.msd_chain(chain_d1, self.criterionGAN, side=g_pre)
         else:
             # D2's update: two lanes (scale 0 | scales 1, 2) beside the WHOLE D1 chain (update, Adam, generator-step pass); the launch
             # stream joins them when D1's chain is through, runs Adam(D2), and D2's forward of the generator step goes on as one lane
-            # under the generator's backward
+            # under the generator's backward.  (Measured, round 6: the whole D2 chain as ONE lane is ~2.5 ms of dependent small launches
+            # and becomes the step's critical path, 6.00 against 5.41 ms; three update lanes or other groupings 5.48 - 5.97 ms; the
+            # generator-step forward as three lanes IN FRONT of the backward + 0.11 ms: profiles/r06a_experiments.md section 2.)
             D2, upd = chain_d2["D"], chain_d2["update"]
             engine._prepare_passes([(D2, upd)])
 
@@ -970,24 +947,19 @@ class SinSKITGModel(BaseModel):
                             engine._scale_lane(D2, sc, upd, self.criterionGAN, knocked_out=(chain_d2["index0"] + sc) in engine.KO_LANES)
                         ops.wgrad_flush(ops.WS_LANE)
                 return run
-            spec = tune.get("VTS_D2_LANES", "")        # measurement: "0|1|2", "0,1,2", ... (default: scale 0 | the others)
-            groups = ([[int(t) for t in g.split(",")] for g in spec.split("|")] if spec else [[0], list(range(1, D2.num_D))])
             lanes = []
             try:
-                for g in groups:
+                for g in ([0], list(range(1, D2.num_D))):
                     if g:
                         lanes.append(engine.fork_lane(d2_update(g)))
-                engine.msd_chain(chain_d1, self.criterionGAN, side=g_pre, serial=tune.get("VTS_D1_SERIAL", "0") == "1")
+                engine.msd_chain(chain_d1, self.criterionGAN, side=g_pre)
             finally:
                 for h in reversed(lanes):      # (also on an exception: an open lane would keep its side stream reserved for good)
                     engine.join_lane(h)
             engine._finish_passes([(D2, upd)])
             chain_d2["mid"]()
-            if tune.get("VTS_D2_TAIL", "lane") == "front":      # measurement: D2's generator-step forward as three lanes IN FRONT of the backward
-                engine.msd_multi([(D2, chain_d2["gstep"]())], self.criterionGAN)
-            else:
-                tail = dict(chain_d2, update=[], mid=lambda: None)
-                self._d2_lane = engine.fork_lane(lambda: engine.msd_chain(tail, self.criterionGAN, serial=True))
+            tail = dict(chain_d2, update=[], mid=lambda: None)
+            self._d2_lane = engine.fork_lane(lambda: engine.msd_chain(tail, self.criterionGAN, serial=True))
         self._chains_done = True
 
     def _d1_pyramid(self, rows, pool_fake):
@@ -1050,15 +1022,11 @@ class SinSKITGModel(BaseModel):
                 d_patch = torch.empty(P, 2, 32, 32, device=dev)
             # (the two channels of the P patches as ONE batch of 2 P single-channel images -- [P, 2, 32, 32] is [2 P, 1, 32, 32] in memory --:
             #  the term is a sum over patches and channels, so one call with twice the batch replaces two; the small maps of the deep
-            #  VGG layers get twice the workgroups.  VTS_LPIPS_T_SPLIT=1: one call per channel, as in round 3)
+            #  VGG layers get twice the workgroups: 67.7 -> 65.9 ms per step against one call per channel, round 4)
+            #  (all three tensors are whole contiguous buffers: fake_T_concat, the patch set's real_T, d_patch; view() refuses anything else)
             f, r = self.fake_T_concat, ts["real_T"]
-            if tune.get("VTS_LPIPS_T_SPLIT", "0") != "1" and f.is_contiguous() and r.is_contiguous() and d_patch.is_contiguous():
-                P_.lpips_term(self.netLPIPS, f.view(2 * P, 1, 32, 32), r.view(2 * P, 1, 32, 32), opt.lambda_G2_lpips / n, slot["G2_lpips"],
-                              grad_into=d_patch.view(2 * P, 1, 32, 32), grad_accumulate=have)
-            else:
-                for c in (0, 1):
-                    P_.lpips_term(self.netLPIPS, f[:, c:c + 1], r[:, c:c + 1], opt.lambda_G2_lpips / n, slot["G2_lpips"],
-                                  grad_into=d_patch[:, c:c + 1], grad_accumulate=have)
+            P_.lpips_term(self.netLPIPS, f.view(2 * P, 1, 32, 32), r.view(2 * P, 1, 32, 32), opt.lambda_G2_lpips / n, slot["G2_lpips"],
+                          grad_into=d_patch.view(2 * P, 1, 32, 32), grad_accumulate=have)
         if d_patch is not None:
             d_fake_T = torch.empty(n, 2, h, w, device=dev)
             ops.patch_scatter_bwd(d_patch, 0, 2, ts["offx"], ts["offy"], nt, 32, d_fake_T)
@@ -1076,7 +1044,7 @@ class SinSKITGModel(BaseModel):
             in0, in1 = self._d1_pair(self.real_S, self.fake_I)
             jobs.append((self.netD, [dict(in0=in0, in1=in1, real=True, coeff=lam, slot=slot["G_GAN"], grad_coeff=lam,
                                           param_grads=False, input_grad=(self._d_fake_I, self._have_dI),
-                                          pyr=self._d1_pyramid(self.real_S.shape[0], pool_fake=False), defer_merge=FUSE_MERGE)]))
+                                          pyr=self._d1_pyramid(self.real_S.shape[0], pool_fake=False), defer_merge=True)]))
             self._g_gan_pass = jobs[-1][1][0]      # (its last merge level rides in g_out_grad: _g_backward)
             self._have_dI = True
         d2_lane = None
@@ -1084,7 +1052,7 @@ class SinSKITGModel(BaseModel):
             self.optimizer_D2.step(self._gscale, bump=False)
             # G2 GAN term: fake_T_concat is detached in the reference (:1751) -> value only
             g2 = dict(in0=self._fake_stack, real=True, coeff=opt.lambda_G2_GAN * nt, slot=slot["G2_GAN"])
-            if D2_TAIL_LANE and engine.PARALLEL_SCALES and not getattr(self.netD2, "is_stylegan2_d", False):
+            if engine.PARALLEL_SCALES and not getattr(self.netD2, "is_stylegan2_d", False):
                 # a logged value that nothing of the step waits for: one lane that stays open under the generator's backward of this
                 # segment instead of three lanes in front of it (round 6; the chained single-GPU step does the same)
                 tail = dict(D=self.netD2, index0=3 if "D" in self.model_names else 0, update=[], mid=lambda: None, gstep=lambda: [g2])

@@ -195,12 +195,10 @@ def unet_desc(G, x, g_out, style_tile=None, side_stream=None):
     return d
 
 
-UNET_C = tune.get("VTS_UNET_C", "1") != "0"     # inference forward through the network-level C entry (0: the Python schedule)
-
-
 def unet_c_ok(G, style_code):
-    """can vts_unet_forward run this generator's inference forward?  (plain U-Net, or the style code tiled into the innermost block)"""
-    if not UNET_C or G.num_downs > L.UNET_MAX_DOWNS:
+    """can vts_unet_forward run this generator's inference forward?  (plain U-Net, or the style code tiled into the innermost block;
+    every other configuration keeps the Python schedule, which measured the same speed: 0.201 vs 0.200 ms per image, bit-identical)"""
+    if G.num_downs > L.UNET_MAX_DOWNS:
         return False
     if G.num_layer_separate >= G.num_downs:     # no shared decoder trunk (every up block duplicated): the C entry's check() refuses it
         return False
@@ -957,7 +955,7 @@ PARALLEL_SCALES = tune.get("VTS_PARALLEL_SCALES", "1") != "0"
 _SIDE_STREAMS = {}
 
 
-SIDE_QUEUES = int(tune.get("VTS_SIDE_QUEUES", "2"))     # round 4: 5.65 -> 5.59 ms (three: 5.61)
+SIDE_QUEUES = 2     # round 4: one -> two 5.65 -> 5.59 ms (three: 5.61); round 6, chained schedule: one / three + 0.04 / + 0.05 ms
 
 
 class SideQueue:
@@ -974,8 +972,8 @@ class SideQueue:
         side = _SIDE_STREAMS.setdefault(torch.cuda.current_device(), [])
         while len(side) < SideQueue.LANE:
             side.append(torch.cuda.Stream())
-        # VTS_SIDE_QUEUES=2: items alternate between two streams (scratch / partial-arena index = the stream's lane number)
-        self.lanes = [SideQueue.LANE - k for k in range(max(1, SIDE_QUEUES))]
+        # items alternate between two streams (scratch / partial-arena index = the stream's lane number)
+        self.lanes = [SideQueue.LANE - k for k in range(SIDE_QUEUES)]
         self.streams = [side[ln - 1] for ln in self.lanes]
         self.turn = 0
         self.keep = []
@@ -1113,7 +1111,7 @@ def _pyramid(D, in0, in1):
 
 
 FLAT_D = tune.get("VTS_FLAT_D", "1") != "0"
-FLAT_MIN_C = int(tune.get("VTS_FLAT_MIN_C", "64"))   # small maps: channels from which the flattened GEMM-class kernel takes over
+FLAT_MIN_C = 64   # small maps: channels from which the flattened GEMM-class kernel takes over (32, the D2 patch layers too: no gain, 10.7 vs 10.6 ms)
 
 
 WIDE_MIN_CI = int(tune.get("VTS_WIDE_MIN_CI", "64"))   # round 3 A/B: 32 / 64 (D1 layer 3 on the GEMM-class kernels) costs + 1.0 - 1.4 ms per step
@@ -1491,7 +1489,7 @@ KO_LANES = tuple(int(k) for k in tune.get("VTS_KO_LANES", "").split(",") if k)
 if KO_LANES:      # timing experiment (tools/probes/r02_ko.sh): the named discriminator lanes are skipped, losses and gradients are WRONG
     import sys
     print("WARNING: VTS_KO_LANES=%s -- discriminator lanes are knocked out, this run's results are wrong (timing experiment only)"
-          % tune.get("VTS_KO_LANES", ""), file=sys.stderr, flush=True)
+          % ",".join(str(k) for k in KO_LANES), file=sys.stderr, flush=True)
 
 
 LANE_STREAMS = int(tune.get("VTS_LANE_STREAMS", "4"))

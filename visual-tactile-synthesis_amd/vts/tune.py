@@ -1,7 +1,9 @@
-"""Experiment switches of the Python layer (schedules, lane packing, kernel-family thresholds, "run the round-3 path" knobs).
+"""Experiment switches of the Python layer: the ones a test or bench.py drives (the serial / joined / chained schedules, lane packing,
+the fresh-batch paths, the kernel-family forms compared bit for bit) and the measuring instruments (VTS_KO_LANES, VTS_KNOCKOUT, which
+knowingly break the arithmetic for timing experiments).  README.md "Switches" lists them all.  Switches whose variant was measured,
+lost and written up (profiles/HISTORY.md, profiles/r06a_experiments.md) are retired: the code runs the winner.
 
-They exist for same-box A/B measurements (tools/ab_env.sh, tools/probes/*) and the bit-compatibility tests between two schedules; two of
-them (VTS_KO_LANES, VTS_KNOCKOUT) knowingly break the arithmetic for timing experiments.  None is a user option, so they are read from
+None is a user option, so they are read from
 the environment ONLY while VTS_TUNING=1 is set: without it every switch has its measured default and a stray VTS_* variable in a user's
 shell changes nothing.  (The C library has the same rule at compile time: csrc/vts_internal.h:vts_tune, make PROFILING=1.)
 

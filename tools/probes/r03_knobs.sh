@@ -6,6 +6,5 @@ run A=1
 run VTS_WGRAD_NS_WGS=256
 run VTS_WGRAD_NS_WGS=384
 run VTS_WGRAD_CAP_MB=4
-run VTS_FUSE_STATS=0
 run A=2
 cat $O

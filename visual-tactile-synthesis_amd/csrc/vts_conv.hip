@@ -268,8 +268,7 @@ static int conv4x4_impl(const vts_conv_desc* d, void* stream, const vts_norm_des
   k.ablate = ablate;
   k.trace = nullptr;
 #endif
-  static const int xcd_swizzle = vts_tune("VTS_XCD_SWIZZLE", 1);
-  k.xcd_swizzle = xcd_swizzle;
+  k.xcd_swizzle = 1;   // XCD-aware workgroup order (the hardware order measured + 0.5 % on the step, round 5)
   static const int direct_epi = vts_tune("VTS_DIRECT_EPI", 1);
   k.direct_epi = direct_epi && (int64_t)d->Cout * d->OH * d->OW * 4 < (int64_t)OOB_OFF && (!d->dmask.data || (int64_t)d->dmask.C * d->OH * d->OW * 4 < (int64_t)OOB_OFF);
   k.ident = vts_ident();
@@ -285,12 +284,10 @@ static int conv4x4_impl(const vts_conv_desc* d, void* stream, const vts_norm_des
   const int nr = (d->Cout + 15) / 16;
   const int N = d->N;
   // statistics of the output in the epilogue (round 3): only the plain "store acc + bias" form through the direct epilogue
-  static const int fuse_stats = vts_tune("VTS_FUSE_STATS", 1);
-  const bool stats_ok = nd && fused && sw.p && fuse_stats && d->act_out == VTS_ACT_NONE && !d->dmask.data && !d->accumulate &&
+  const bool stats_ok = nd && fused && sw.p && d->act_out == VTS_ACT_NONE && !d->dmask.data && !d->accumulate &&
                         nd->x == d->out && nd->N == N && nd->C == d->Cout && nd->HW == d->OH * d->OW && nd->nstride == d->out_nstride;
   const bool want_stats = stats_ok && k.direct_epi && sw.floats >= vts_conv4x4_norm_ws_floats(d);
-  static const int fuse_bsums = vts_tune("VTS_FUSE_BSUMS", 1);
-  const bool bsums_ok = bsums && fused && sw.p && fuse_bsums && d->act_out == VTS_ACT_NONE && d->dmask.data;
+  const bool bsums_ok = bsums && fused && sw.p && d->act_out == VTS_ACT_NONE && d->dmask.data;
   const bool want_bsums = bsums_ok && k.direct_epi && sw.floats >= vts_conv4x4_norm_ws_floats(d);
   {
     // thin stride-2 convolutions / transposed convolutions on full-size maps: the lane = pixel members (vts_conv_px.hip), with the same
@@ -314,8 +311,7 @@ static int conv4x4_impl(const vts_conv_desc* d, void* stream, const vts_norm_des
     const int GH = ph4 ? (d->OH + 1) / 2 : d->OH, GW = ph4 ? (d->OW + 1) / 2 : d->OW;
     const int full_wgs = cdiv(GW, 16 * mt) * cdiv(GH, 4 * rw) * N;
     // input channels per pipeline step of the split instance: 8 where the slice is long enough (the per-chunk cost -- two barriers, the
-    // staging stores, the descriptor arithmetic: 0.25 - 0.5 us measured -- is paid half as often); VTS_SPLIT_CK=4: always 4
-    static const int split_ck = vts_tune("VTS_SPLIT_CK", 8);
+    // staging stores, the descriptor arithmetic: 0.25 - 0.5 us measured -- is paid half as often; always 4 measured +- 0 on the step, round 5)
     int ck = 4;
     const int nchunks = (k.Cin + 3) / 4;
     static const int small_thr = vts_tune("VTS_SMALL_WGS", 300);   // < ~1.2 workgroups per CU: split (measured: 128 -> 300 = step 7.88 -> 7.51 ms)
@@ -331,7 +327,7 @@ static int conv4x4_impl(const vts_conv_desc* d, void* stream, const vts_norm_des
       if (KS > 1 && (!d->ws || d->ws_floats < need)) { KS = 1; cps = nchunks; }
       // (the slices are cut in 4-channel units as before; an even slice of >= 16 channels runs as 8-channel steps: same partition, same
       //  accumulation order, bit-identical results)
-      if (split_ck == 8 && k.Cin >= 32 && cps >= 4 && (cps % 2 == 0 || KS == 1)) { ck = 8; cps = (cps + 1) / 2; }   // (20 -> 40 at 256^2 measured 15 % slower in 8-channel steps)
+      if (k.Cin >= 32 && cps >= 4 && (cps % 2 == 0 || KS == 1)) { ck = 8; cps = (cps + 1) / 2; }   // (20 -> 40 at 256^2 measured 15 % slower in 8-channel steps)
       k.CG = nr; k.cps = cps; k.part = KS > 1 ? d->ws : nullptr;
       const bool cg_stats = want_stats && KS == 1;    // output-channel split only: every workgroup still stores final values
       if (cg_stats) k.stat_part = sw.p;
@@ -352,8 +348,7 @@ static int conv4x4_impl(const vts_conv_desc* d, void* stream, const vts_norm_des
         *fused = 1;
         return VTS_OK;
       }
-      static const int fuse_inbwd = vts_tune("VTS_FUSE_SPLIT_INBWD", 1);
-      if (bsums && in_bwd_ok && fused && fuse_inbwd && (int64_t)d->OH * d->OW <= 4096 && d->act_out == VTS_ACT_NONE && d->dmask.data && d->dmask.scale &&
+      if (bsums && in_bwd_ok && fused && (int64_t)d->OH * d->OW <= 4096 && d->act_out == VTS_ACT_NONE && d->dmask.data && d->dmask.scale &&
           d->dmask.shift && d->dmask.C == d->Cout) {
         hipLaunchKernelGGL(conv_split_epilogue_inbwd_kernel, dim3(N * d->Cout), dim3(256), 0, st, k, KS);
         VTS_CHECK_LAUNCH("vts_conv4x4 split epilogue + instance norm backward");

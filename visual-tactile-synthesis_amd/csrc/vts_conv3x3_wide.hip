@@ -675,10 +675,9 @@ static int wide_launch(WideK& k, int S, float* ws, int64_t ws_floats, hipStream_
   k.KS = KS; k.cps = cps; k.part = KS > 1 ? ws : nullptr;
   dim3 grid(cdiv(k.W, TX) * cdiv(k.H, TY), cdiv(k.Cout, TCO), k.N * KS);
   // maps whose 4 x 32 tiling wastes >= 10 %% more than runs of 128 flattened pixels (and whose rows fit the patch): the row-run kernel
-  static const int no_rowrun = vts_tune_set("VTS_NO_ROWRUN") ? 1 : 0;
   const double eff_tile = (double)k.W * k.H / ((double)cdiv(k.W, TX) * TX * cdiv(k.H, TY) * TY);
   const double eff_run = (double)k.W * k.H / (128.0 * cdiv(k.W * k.H, 128));
-  if (!no_rowrun && S == 1 && k.os == 1 && k.ntaps == TW && k.W >= 64 && ck * rr_rows(k.W, K) * ((k.IPW + 3) & ~3) <= RR_PATCH_FLOATS &&
+  if (S == 1 && k.os == 1 && k.ntaps == TW && k.W >= 64 && ck * rr_rows(k.W, K) * ((k.IPW + 3) & ~3) <= RR_PATCH_FLOATS &&
       k.OH == k.H && k.OW == k.W && eff_run > 1.1 * eff_tile) {
     grid.x = cdiv(k.W * k.H, 128);
     if (K == 4) hipLaunchKernelGGL(conv4x4_rowrun_kernel, grid, dim3(256), 0, st, k);

@@ -8,7 +8,8 @@
 //   Y = A^T [ sum_ci (G g G^T) . (B^T d B) ] A       d: 4 x 4 input patch, g: 3 x 3 taps, Y: 2 x 2 outputs, '.' elementwise
 //
 // Weights are transformed once (the stacks are frozen): U[ci][p][co], p = 4 i + j the position in the 4 x 4 transform domain.
-// Kernel: a workgroup (4 waves, ONE per SIMD: the 16 accumulator tiles of a wave fill the 256 accumulation registers) owns 64 output
+// First kernel (conv3x3_wino_kernel, retired: 11 - 19 % slower than the eight-wave form below on every layer of the table in
+// profiles/HISTORY.md, round 4): a workgroup (4 waves, ONE per SIMD: the 16 accumulator tiles of a wave fill the 256 accumulation registers) owns 64 output
 // channels x 64 tiles (8 x 8 tiles = 16 x 16 output pixels) of one image.  Per chunk of 8 input channels it transforms the 512
 // (channel, tile) patches to V[p][ci][tile] in LDS (two per thread, straight from global memory: rows of four floats at even columns),
 // stages U[p][ci][co] beside it, and runs 16 positions x 4 k-steps of v_mfma_f32_32x32x2_f32 (64 per wave and chunk: a 64 x 64 x 8 GEMM per
@@ -44,154 +45,6 @@ constexpr int CKW = 8, TCO = 64, TT = 64;     // channels per chunk, output chan
 
 __device__ __forceinline__ f32x4 ld4(const rsrc_t& rs, int byte_off) {
   return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, byte_off, 0, 0));
-}
-
-__global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(const WinoK p) {
-  __shared__ __attribute__((aligned(16))) float lds[2 * 16 * CKW * 64];
-  float* lds_u = lds;                       // [p][ci][64 co]
-  float* lds_v = lds + 16 * CKW * 64;       // [p][ci][64 tiles]
-  const int tid = threadIdx.x, lane = tid & 63, l32 = lane & 31, kh = lane >> 5;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int mi = wave & 1, ni = wave >> 1;
-  const int bx_n = (p.W + 15) >> 4;
-  const int bx = blockIdx.x % bx_n, by = blockIdx.x / bx_n;
-  const int x0 = bx * 16, y0 = by * 16, co0 = blockIdx.y * TCO, n = blockIdx.z;
-  const int plane = p.IPH * p.IPW;
-  const int nchunks = (p.Cin + CKW - 1) / CKW;
-
-  // buffer resources: the whole input from this image on (a patch row beyond the map reads the next plane -- finite garbage that only
-  // reaches outputs beyond the map, which are not stored; beyond the tensor: zeros), the transformed weights
-  const int64_t in_floats = (int64_t)(p.N - n) * p.Cin * plane;
-  const auto rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in) + (int64_t)n * p.Cin * plane, 0,
-                                                       (int)(in_floats * 4 > 0x7fffffff ? 0x7fffffff : in_floats * 4), RSRC_FLAGS);
-  const auto rs_u = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.U), 0, nchunks * CKW * 16 * p.Cout * 4, RSRC_FLAGS);
-
-  // this thread's two (channel, tile) patches of a chunk and its eight weight quads
-  int doff[2];
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    const int j = tid + e * 256, ci = j >> 6, t = j & 63, ty = t >> 3, tx = t & 7;
-    doff[e] = (ci * plane + (y0 + 2 * ty) * p.IPW + x0 + 2 * tx) * 4;
-  }
-  int uoff[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int idx = tid + e * 256, row = idx >> 4, q = idx & 15;     // row = ci * 16 + p of the chunk, 16 quads of output channels
-    uoff[e] = (row * p.Cout + co0 + 4 * q) * 4;
-  }
-  f32x4 dreg[2][4], ureg[8];
-  auto load_chunk = [&](int c) {
-    const int cb = c * CKW * plane * 4, ub = c * CKW * 16 * p.Cout * 4;
-#pragma unroll
-    for (int e = 0; e < 2; ++e)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) dreg[e][r] = ld4(rs_in, cb + doff[e] + r * p.IPW * 4);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) ureg[e] = ld4(rs_u, ub + uoff[e]);
-  };
-  auto store_chunk = [&]() {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int idx = tid + e * 256, row = idx >> 4, q = idx & 15, ci = row >> 4, pp = row & 15;
-      *reinterpret_cast<f32x4*>(lds_u + (pp * CKW + ci) * 64 + 4 * q) = ureg[e];
-    }
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int j = tid + e * 256, ci = j >> 6, t = j & 63;
-      // V = B^T d B
-      float tt[4][4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float d0 = dreg[e][0][c], d1 = dreg[e][1][c], d2 = dreg[e][2][c], d3 = dreg[e][3][c];
-        tt[0][c] = d0 - d2; tt[1][c] = d1 + d2; tt[2][c] = d2 - d1; tt[3][c] = d1 - d3;
-      }
-      float* v = lds_v + ci * 64 + t;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        v[((4 * i + 0) * CKW) * 64] = tt[i][0] - tt[i][2];
-        v[((4 * i + 1) * CKW) * 64] = tt[i][1] + tt[i][2];
-        v[((4 * i + 2) * CKW) * 64] = tt[i][2] - tt[i][1];
-        v[((4 * i + 3) * CKW) * 64] = tt[i][1] - tt[i][3];
-      }
-    }
-  };
-
-  f32x16 acc[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-
-  load_chunk(0);
-  for (int c = 0; c < nchunks; ++c) {
-    store_chunk();
-    __syncthreads();
-    if (c + 1 < nchunks) load_chunk(c + 1);
-    const float* ua = lds_u + kh * 64 + mi * 32 + l32;
-    const float* vb = lds_v + kh * 64 + ni * 32 + l32;
-#pragma unroll
-    for (int pp = 0; pp < 16; ++pp)
-#pragma unroll
-      for (int ks = 0; ks < CKW / 2; ++ks) {
-        const float a = ua[(pp * CKW + 2 * ks) * 64], b = vb[(pp * CKW + 2 * ks) * 64];
-        acc[pp] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[pp], 0, 0, 0);
-      }
-    __syncthreads();
-  }
-
-  // output transform Y = A^T M A per (channel, tile); C layout of a 32 x 32 tile: column (tile) = lane % 32, row (channel) =
-  // (r / 4) * 8 + (lane / 32) * 4 + r % 4
-  const int t = ni * 32 + l32, ty = t >> 3, tx = t & 7;
-  const int oy = y0 + 2 * ty, ox = x0 + 2 * tx;
-  const int64_t oplane = (int64_t)p.OH * p.OW;
-  float* ob = p.out + (int64_t)n * p.Cout * oplane;
-  if (oy < p.H && ox < p.W) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int co = co0 + mi * 32 + (r >> 2) * 8 + kh * 4 + (r & 3);
-      float s[2][4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        s[0][j] = acc[j][r] + acc[4 + j][r] + acc[8 + j][r];
-        s[1][j] = acc[4 + j][r] - acc[8 + j][r] - acc[12 + j][r];
-      }
-      const float bsv = p.bias ? p.bias[co] : 0.f;
-#pragma unroll
-      for (int a = 0; a < 2; ++a) {
-        float y[2] = {s[a][0] + s[a][1] + s[a][2] + bsv, s[a][1] - s[a][2] - s[a][3] + bsv};
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-          const int yy = oy + a, xx = ox + b;
-          if (yy < p.H && xx < p.W) {
-            const int64_t o = co * oplane + (int64_t)(p.oy0 + yy) * p.OW + p.ox0 + xx;
-            float v = y[b];
-            if (p.ep_mode == 1) v = fmaxf(v, 0.f);
-            if (p.ep_mode == 2) {
-              const int64_t e = (int64_t)n * p.Cout * oplane + o;
-              v = p.ep_mask[e] > 0.f ? v + (p.ep_add ? p.ep_add[e] : 0.f) : 0.f;
-            }
-            ob[o] = v;
-            if (p.ep_mode) {      // padded output: the pixels on the rim of the map also store the zero border next to them
-              float* q = ob + o;
-              const bool xl = xx == 0, xr = xx == p.W - 1;
-              if (xl) q[-1] = 0.f;
-              if (xr) q[1] = 0.f;
-              if (yy == 0) {
-                q[-p.OW] = 0.f;
-                if (xl) q[-p.OW - 1] = 0.f;
-                if (xr) q[-p.OW + 1] = 0.f;
-              }
-              if (yy == p.H - 1) {
-                q[p.OW] = 0.f;
-                if (xl) q[p.OW - 1] = 0.f;
-                if (xr) q[p.OW + 1] = 0.f;
-              }
-            }
-          }
-        }
-      }
-    }
-  }
 }
 
 // The same tile on EIGHT waves (two per SIMD, round 4).  With one wave per SIMD the phases of a chunk run one after the other -- ablation:
@@ -574,10 +427,9 @@ extern "C" int vts_w3x3_wino_pack(const float* w, int A, int B, int64_t sa, int6
 
 // shapes the kernel takes: 64-channel output groups, maps that give the chip enough 16 x 16 blocks, operands inside 31-bit byte offsets
 // flat-tile mode: maps of at most 16 x 16 pixels whose batch gives the chip >= 128 workgroups of 64 tiles x 64 channels, the whole input
-// inside 31-bit byte offsets (VTS_WINO_FLAT=0: off)
+// inside 31-bit byte offsets (without it: the reference-default step 63.6 vs 58.6 ms, round 4)
 static bool wino_flat(int N, int Cin, int Cout, int H, int W) {
-  static const int off = vts_tune("VTS_WINO_FLAT", 1) == 0;
-  if (off || H > 16 || W > 16 || (H == 16 && W == 16)) return false;
+  if (H > 16 || W > 16 || (H == 16 && W == 16)) return false;
   if ((int64_t)N * ((Cin + 7) / 8 * 8) * (H + 2) * (W + 2) * 4 > 0x7fffffffll) return false;
   const int64_t tiles = (int64_t)N * cdiv(H, 2) * cdiv(W, 2);
   return cdiv64(tiles, 64) * (Cout / TCO) >= 128;
@@ -609,22 +461,20 @@ extern "C" int vts_conv3x3_wino(const float* in, const float* U, const float* bi
   k.flat = wino_flat(N, Cin, Cout, H, W) ? 1 : 0;
   k.tiles_x = cdiv(W, 2); k.tpi = k.tiles_x * cdiv(H, 2); k.ntiles = N * k.tpi;
   const dim3 grid = k.flat ? dim3(cdiv(k.ntiles, 64), Cout / TCO, 1) : dim3(cdiv(W, 16) * cdiv(H, 16), Cout / TCO, N);
-  static const int v1 = vts_tune_set("VTS_WINO_V1") ? 1 : 0;      // the one-wave-per-SIMD kernel (A/B timing)
-  if (v1 && !k.flat) {
-    hipLaunchKernelGGL(conv3x3_wino_kernel, grid, dim3(256), 0, (hipStream_t)stream, k);
-    vts_set_kernel("conv3x3_wino_kernel");
-  } else {
-    constexpr int LDS_BYTES = 2 * 2 * 16 * CKW * 64 * 4;       // 128 KB: two buffers of the weight and the patch tile
-    static const int ablate = vts_tune("VTS_WINO_ABLATE", 0);
-    void (*kern)(const WinoK) = ablate == 1 ? conv3x3_wino8_kernel<1> : ablate == 8 ? conv3x3_wino8_kernel<8> : ablate == 9 ? conv3x3_wino8_kernel<9> : conv3x3_wino8_kernel<0>;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (attr != hipSuccess) {
-      vts_set_error("vts_conv3x3_wino: %d bytes of LDS per workgroup refused: %s", LDS_BYTES, hipGetErrorString(attr));
-      return VTS_ERR_LAUNCH;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(512), LDS_BYTES, (hipStream_t)stream, k);
-    vts_set_kernel("conv3x3_wino8_kernel");
+  constexpr int LDS_BYTES = 2 * 2 * 16 * CKW * 64 * 4;       // 128 KB: two buffers of the weight and the patch tile
+#ifdef VTS_PROFILING
+  static const int ablate = vts_tune("VTS_WINO_ABLATE", 0);
+  void (*kern)(const WinoK) = ablate == 1 ? conv3x3_wino8_kernel<1> : ablate == 8 ? conv3x3_wino8_kernel<8> : ablate == 9 ? conv3x3_wino8_kernel<9> : conv3x3_wino8_kernel<0>;
+#else
+  void (*kern)(const WinoK) = conv3x3_wino8_kernel<0>;     // (the ablation instances exist in the instrumented build only)
+#endif
+  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+  if (attr != hipSuccess) {
+    vts_set_error("vts_conv3x3_wino: %d bytes of LDS per workgroup refused: %s", LDS_BYTES, hipGetErrorString(attr));
+    return VTS_ERR_LAUNCH;
   }
+  hipLaunchKernelGGL(kern, grid, dim3(512), LDS_BYTES, (hipStream_t)stream, k);
+  vts_set_kernel("conv3x3_wino8_kernel");
   VTS_CHECK_LAUNCH("vts_conv3x3_wino");
   return VTS_OK;
 }
@@ -632,8 +482,7 @@ extern "C" int vts_conv3x3_wino(const float* in, const float* U, const float* bi
 // Internal (vts_conv3x3_wide.hip: vts_wgrad3x3_wide): partials of the stride-1 weight gradient in Winograd form into part [KS][Cout][Cin][9]
 // with KS <= max_ks slices; returns the number of slices written, 0 if the shape is not taken.
 int vts_wgrad3x3_wino_try(const float* dout, const float* in, float* part, int N, int Cin, int Cout, int H, int W, int max_ks, hipStream_t st) {
-  static const int off = vts_tune("VTS_WINO", 1) == 0 ? 1 : (vts_tune("VTS_WINO_WGRAD", 1) == 0 ? 1 : 0);
-  if (off || Cin < 64 || Cout < 64 || H < 8 || W < 8 || max_ks < 1) return 0;
+  if (Cin < 64 || Cout < 64 || H < 8 || W < 8 || max_ks < 1) return 0;
   if ((int64_t)N * Cin * (H + 2) * (W + 2) * 4 > 0x7fffffe0ll || (int64_t)N * Cout * H * W * 4 > 0x7fffffe0ll) return 0;
   WinoWgK k{};
   k.dout = dout; k.in = in; k.part = part; k.N = N; k.Cin = Cin; k.Cout = Cout; k.H = H; k.W = W;

@@ -30,7 +30,7 @@ struct ConvK {
   float slope_in;      // input activation as t > 0 ? t : slope * t
   int identity_in;     // no affine on either source and no input activation
   int wbytes;       // extent of the weight tensor view in bytes (buffer descriptor of the weight loads)
-  int xcd_swizzle;  // 1: XCD-aware workgroup order (default); VTS_XCD_SWIZZLE=0 keeps the hardware order
+  int xcd_swizzle;  // 1: XCD-aware workgroup order (what the host sets); 0 keeps the hardware order
   int direct_epi;   // 1: stores straight from the accumulator registers (default); 0: through LDS (VTS_DIRECT_EPI=0)
   int tiles_x;      // tiles per row band; a workgroup walks the run [bx * tiles_x / gridDim.x, (bx + 1) * tiles_x / gridDim.x) of them
   // round 3: statistics of the output fused into the direct epilogue.  Every WAVE writes (mean, M2, count) of its rows of the tile per
@@ -826,12 +826,11 @@ __global__ __launch_bounds__(256, conv_min_waves(MODE, S, NR, RW, MT, RUN)) void
 
 // Tile width by map width (round 3): the discriminator maps are 513 / 257 / 129 / 130 / 65 / 66 / 33 / 34 wide, and a 64-column tile
 // covers 129 columns with 192 (a third of every MFMA row group multiplies nothing).  Where three 16-column groups per tile (48 columns)
-// cover the row with >= 7 % fewer columns than the table's width, the dispatch takes the MT = 3 instance (VTS_MT3=0: never).
+// cover the row with >= 7 % fewer columns than the table's width, the dispatch takes the MT = 3 instance (never: + 1.4 % on the step, round 5).
 inline bool vts_prefer_mt3(const ConvK& k, bool phases4, int mt_default) {
-  static const int on = vts_tune("VTS_MT3", 1);
   const int GW = phases4 ? (k.OW + 1) / 2 : k.OW;
   const int c3 = cdiv(GW, 48) * 48, cd = cdiv(GW, 16 * mt_default) * 16 * mt_default;
-  return on && c3 * 100 < cd * 93;
+  return c3 * 100 < cd * 93;
 }
 
 template <int MODE, int S, int NR, int RW, int MT, int CK>
@@ -844,16 +843,14 @@ int launch(const ConvK& k0, int N, hipStream_t st, int CG = 1, int KS = 1) {
   k.stat_spl = tiles_x * tiles_y;      // one statistics / backward-sum slot per workgroup tile (round 4; one per wave before)
   t_stat_spl = k.stat_spl;
   // Tile runs: only where the per-tile chunk pipeline is too short to overlap anything (<= run_max_chunks chunks per tile) and
-  // the grid stays several workgroups per CU deep after the cut.  VTS_TILE_RUN=<n> forces a run length (1 = one tile per workgroup).
-  static const int run_force = vts_tune("VTS_TILE_RUN", 0);
-  static const int run_wgs = vts_tune("VTS_TILE_RUN_WGS", 2048);
-  static const int run_max_chunks = vts_tune("VTS_TILE_RUN_CHUNKS", 4);
+  // the grid stays several workgroups per CU deep after the cut.  (Forced runs on the multi-chunk layers measured 1.2 - 2.7x slower.)
+  constexpr int run_wgs = 2048;        // workgroups left after the cut (1024 / 4096: +- 0.3 % on the step, round 5)
+  constexpr int run_max_chunks = 4;    // (2 chunks: +- 0.3 % on the step, round 5)
   int run = 1;
   if (NR <= 2 && !k.part && k.direct_epi && KS == 1) {
     const int64_t total = (int64_t)tiles_x * tiles_y * N * CG;
     const int nchunks = (k.Cin + CK - 1) / CK;
-    if (run_force > 0) run = run_force;
-    else if (nchunks <= run_max_chunks) run = (int)(total / run_wgs);
+    if (nchunks <= run_max_chunks) run = (int)(total / run_wgs);
     if (run > tiles_x) run = tiles_x;
     if (run < 1) run = 1;
   }

@@ -422,9 +422,8 @@ int vts_conv_small_try(const vts_conv_desc* d, hipStream_t st) {
   const int upw = cdiv(k.MTP * P, 4);                            // units per wave
   if (upw > 8) return VTS_ERR_UNSUPPORTED;
   const int U = upw <= 1 ? 1 : (upw <= 2 ? 2 : (upw <= 4 ? 4 : 8));
-  static const int fast_on = vts_tune("VTS_SMALL_FLAT", 1);
   k.inbytes = (int)((int64_t)d->N * d->in0.nstride * 4 < (int64_t)0x40000000 ? (int64_t)d->N * d->in0.nstride * 4 : 0);
-  k.fast = fast_on && !d->in1.data && k.Cin % CK == 0 && d->in0.nstride == (int64_t)k.Cin * d->IH * d->IW && (reinterpret_cast<uintptr_t>(d->in0.data) & 15) == 0 &&
+  k.fast = !d->in1.data && k.Cin % CK == 0 && d->in0.nstride == (int64_t)k.Cin * d->IH * d->IW && (reinterpret_cast<uintptr_t>(d->in0.data) & 15) == 0 &&
            ipb * 2 * d->IH * d->IW <= 768 && k.inbytes > 0 && (reinterpret_cast<uintptr_t>(d->w) & 15) == 0 && ((d->ws_co | d->ws_ci) & 3) == 0;
   const size_t lds = (size_t)(ipb * CK * k.plane + CK * 16 * COP + k.MTP * 16 + ipb * CK * d->IH + (k.fast ? 2 * ipb * k.Cin : 0)) * sizeof(float);
 #define SMALL_U(MODE, S, NRV)                                                  \

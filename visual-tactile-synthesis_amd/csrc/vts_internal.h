@@ -27,7 +27,8 @@ int vts_wgrad3x3_wino_try(const float* dout, const float* in, float* part, int N
 bool vts_patchnce_mfma_ok(int P, int D);
 int vts_patchnce_mfma(const float* q, const float* k, int B, int P, int D, float T, float gscale, float* loss, float* dq, hipStream_t st);
 // LeakyReLU slope that expresses the activation codes as  t > 0 ? t : slope * t
-// Tuning / experiment switches (tile tables, thresholds, "run the other kernel" knobs: ~50 VTS_* names across the library) exist only in
+// Tuning / experiment switches (measurement instruments and a few unmeasured "run the other kernel" knobs: 21 VTS_* names across the
+// library, listed in README.md "Switches"; the settled ones are retired, tools/README.md) exist only in
 // the instrumented build (make PROFILING=1 -> libvts_hip_prof.so, loaded through VTS_LIB_PATH by tools/): there they are read from the
 // environment.  The PRODUCTION library reads exactly one environment variable (VTS_RCCL_LIB, the RCCL library to dlopen, vts_comm.cpp);
 // every dispatch decision in it is the measured default, a compile-time constant -- no switch can change what a user's run computes.

@@ -832,7 +832,9 @@ __global__ __launch_bounds__(1024) void norm_bwd_fused_loop_kernel(float* __rest
   }
 }
 
+#ifdef VTS_PROFILING   // (launched only by VTS_NORM_BWD_3K)
 __global__ __launch_bounds__(64) void norm_bwd_finalize_kernel(const float* __restrict__ part, const NormBwdK k) { norm_bwd_finalize_group(part, k, blockIdx.x); }
+#endif
 
 __global__ __launch_bounds__(256) void norm_bwd_partial_kernel(const float* __restrict__ dy, const float* __restrict__ x, int64_t nstride, int C,
                                                                int HW, int spl, const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -1059,18 +1061,20 @@ extern "C" int vts_norm_bwd(const vts_norm_bwd_desc* d, float* ws, void* stream)
   hipLaunchKernelGGL(norm_bwd_partial_kernel, dim3(spl, d->C, d->N), dim3(256), 0, st, d->dy, d->x, d->nstride, d->C, d->HW, spl,
                      d->mean, d->rstd, part);
   VTS_CHECK_LAUNCH("vts_norm_bwd partial");
-  static const int three = vts_tune("VTS_NORM_BWD_3K", 0);   // 1: the separate finalize launch (A/B timing)
-  if (!three) {
-    hipLaunchKernelGGL(norm_bwd_apply_fin_kernel, dim3(spl, d->C, d->N), dim3(256), 0, st, d->dy, d->x, d->nstride, part, k);
+#ifdef VTS_PROFILING
+  static const int three = vts_tune("VTS_NORM_BWD_3K", 0);   // 1: the separate finalize launch (A/B timing; unmeasured, instrumented build only)
+  if (three) {
+    hipLaunchKernelGGL(norm_bwd_finalize_kernel, dim3(d->mode == 0 ? d->N * d->C : d->C), dim3(64), 0, st, part, k);
+    VTS_CHECK_LAUNCH("vts_norm_bwd finalize");
+    hipLaunchKernelGGL(norm_bwd_apply_kernel, dim3(spl, d->C, d->N), dim3(256), 0, st, d->dy, d->x, d->nstride, d->C, d->HW, coef);
     VTS_CHECK_LAUNCH("vts_norm_bwd apply");
-    vts_set_kernel("norm_bwd_partial_kernel+norm_bwd_apply_fin_kernel");
+    vts_set_kernel("norm_bwd_partial_kernel+norm_bwd_finalize_kernel+norm_bwd_apply_kernel");
     return VTS_OK;
   }
-  hipLaunchKernelGGL(norm_bwd_finalize_kernel, dim3(d->mode == 0 ? d->N * d->C : d->C), dim3(64), 0, st, part, k);
-  VTS_CHECK_LAUNCH("vts_norm_bwd finalize");
-  hipLaunchKernelGGL(norm_bwd_apply_kernel, dim3(spl, d->C, d->N), dim3(256), 0, st, d->dy, d->x, d->nstride, d->C, d->HW, coef);
+#endif
+  hipLaunchKernelGGL(norm_bwd_apply_fin_kernel, dim3(spl, d->C, d->N), dim3(256), 0, st, d->dy, d->x, d->nstride, part, k);
   VTS_CHECK_LAUNCH("vts_norm_bwd apply");
-  vts_set_kernel("norm_bwd_partial_kernel+norm_bwd_finalize_kernel+norm_bwd_apply_kernel");
+  vts_set_kernel("norm_bwd_partial_kernel+norm_bwd_apply_fin_kernel");
   return VTS_OK;
 }
 
@@ -1087,22 +1091,15 @@ extern "C" int vts_norm_bwd_from_partials(const vts_norm_bwd_desc* d, const floa
   }
   k.pspl = slots;
   k.beta = beta;
-  static const int wide = vts_tune("VTS_NORM_BWD_SUMS", 1);   // 0: the 2048-element apply kernel (A/B)
-  if (wide) {
-    // elements per workgroup: multiples of 2048, as many as leave >= ~768 workgroups, at most 32 K
-    int chunk = CHUNK;
-    while (chunk < 32768 && (int64_t)cdiv(d->HW, 2 * chunk) * d->C * d->N >= 768) chunk *= 2;
-    const bool vec = d->HW % 4 == 0 && d->nstride % 4 == 0 && ((reinterpret_cast<uintptr_t>(d->dy) | reinterpret_cast<uintptr_t>(d->x)) & 15) == 0;
-    const dim3 grid(cdiv(d->HW, chunk), d->C, d->N);
-    if (vec) hipLaunchKernelGGL(norm_bwd_apply_sums_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, d->dy, d->x, d->nstride, part, k, chunk);
-    else hipLaunchKernelGGL(norm_bwd_apply_sums_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, d->dy, d->x, d->nstride, part, k, chunk);
-    VTS_CHECK_LAUNCH("vts_norm_bwd_from_partials");
-    vts_set_kernel("norm_bwd_apply_sums_kernel");
-    return VTS_OK;
-  }
-  hipLaunchKernelGGL(norm_bwd_apply_fin_kernel, dim3(spl, d->C, d->N), dim3(256), 0, (hipStream_t)stream, d->dy, d->x, d->nstride, part, k);
+  // elements per workgroup: multiples of 2048, as many as leave >= ~768 workgroups, at most 32 K
+  int chunk = CHUNK;
+  while (chunk < 32768 && (int64_t)cdiv(d->HW, 2 * chunk) * d->C * d->N >= 768) chunk *= 2;
+  const bool vec = d->HW % 4 == 0 && d->nstride % 4 == 0 && ((reinterpret_cast<uintptr_t>(d->dy) | reinterpret_cast<uintptr_t>(d->x)) & 15) == 0;
+  const dim3 grid(cdiv(d->HW, chunk), d->C, d->N);
+  if (vec) hipLaunchKernelGGL(norm_bwd_apply_sums_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, d->dy, d->x, d->nstride, part, k, chunk);
+  else hipLaunchKernelGGL(norm_bwd_apply_sums_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, d->dy, d->x, d->nstride, part, k, chunk);
   VTS_CHECK_LAUNCH("vts_norm_bwd_from_partials");
-  vts_set_kernel("norm_bwd_apply_fin_kernel");
+  vts_set_kernel("norm_bwd_apply_sums_kernel");
   return VTS_OK;
 }
 

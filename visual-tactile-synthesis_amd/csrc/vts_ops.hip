@@ -753,8 +753,7 @@ inline unsigned blocks_for(int64_t n, int cap = 2048) {
 extern "C" int vts_avgpool3s2(const float* x, int64_t xns, int N, int C, int H, int W, float* y, void* stream) {
   VTS_CHECK_ARG(x && y && N * C <= 65535, "vts_avgpool3s2: bad args");
   const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
-  static const bool rows4 = !(vts_tune("VTS_AVGPOOL_ROWS4", 1) == 0);
-  if (rows4 && W % 2 == 0 && W >= 4 && (reinterpret_cast<uintptr_t>(x) & 7) == 0 && xns % 2 == 0 && ((int64_t)H * W) % 2 == 0)
+  if (W % 2 == 0 && W >= 4 && (reinterpret_cast<uintptr_t>(x) & 7) == 0 && xns % 2 == 0 && ((int64_t)H * W) % 2 == 0)
     hipLaunchKernelGGL(avgpool_rows4_kernel, dim3(cdiv(OW, 64), cdiv(OH, 16), N * C), dim3(256), 0, (hipStream_t)stream, x, xns, C, H, W,
                        OH, OW, y);
   else

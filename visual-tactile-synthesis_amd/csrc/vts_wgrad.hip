@@ -955,8 +955,7 @@ Plan make_plan(const vts_wgrad_desc* d) {
   const int CL = d->lo0.C + (d->lo1.data ? d->lo1.C : 0), CH = d->hi0.C + (d->hi1.data ? d->hi1.C : 0);
   pl.ns = 0;
   pl.small = 0;
-  static const int use_small = vts_tune("VTS_WGRAD_SMALL", 1);
-  if (use_small && !d->lo1.data && !d->hi1.data && d->N >= 32 && d->LH * d->LW <= 324 && d->HH <= 34 && d->HW <= 34 && CL <= 64 && CH <= 64 &&
+  if (!d->lo1.data && !d->hi1.data && d->N >= 32 && d->LH * d->LW <= 324 && d->HH <= 34 && d->HW <= 34 && CL <= 64 && CH <= 64 &&
       d->pad >= 0 && d->pad <= SW_HALO && d->pad + d->pad_dx >= 0 && d->pad + d->pad_dx <= SW_HALO) {
     const int clt = CL <= 16 ? 1 : (CL <= 32 ? 2 : 4);
     const int need = cdiv(CH, 4);
@@ -983,8 +982,7 @@ Plan make_plan(const vts_wgrad_desc* d) {
       }
     }
   }
-  static const int use_head = vts_tune("VTS_WGRAD_HEAD", 1);
-  if (use_head && CL == 1 && !d->lo1.data && !d->hi1.data && d->stride == 1 && d->act_lo == VTS_ACT_NONE && !d->lo0.scale && !d->lo0.shift &&
+  if (CL == 1 && !d->lo1.data && !d->hi1.data && d->stride == 1 && d->act_lo == VTS_ACT_NONE && !d->lo0.scale && !d->lo0.shift &&
       d->LH >= 8 && d->LW >= 16 && d->act_hi != VTS_ACT_TANH) {
     pl.head = 1;
     pl.clt = pl.cht = pl.cl_groups = pl.ch_groups = 1;
@@ -996,7 +994,7 @@ Plan make_plan(const vts_wgrad_desc* d) {
     return pl;
   }
   static const int use_ns = vts_tune("VTS_WGRAD_NS", 1);
-  static const int ns_min_ch = vts_tune("VTS_WGRAD_NS_MINCH", 2);   // (5 until round 3: 2 - 4 channel layers on the K-split kernel)
+  constexpr int ns_min_ch = 2;   // (5 until round 3: 2 - 4 channel layers on the K-split kernel; 5 against fewer was within the +- 0.15 ms spread in round 2)
   static const int ns_min_w = vts_tune("VTS_WGRAD_NS_MINW", 8);
   // (the buffer-load addressing of the N-split kernel needs channel planes below 2^26 bytes)
   if (use_ns && CH >= ns_min_ch && d->LW > ns_min_w && (int64_t)d->HH * d->HW < (1 << 24) && (int64_t)d->LH * d->LW < (1 << 24)) {
@@ -1134,11 +1132,10 @@ void launch_ns_tall(const WgK& k, const Plan& pl, hipStream_t st) {
 
 // tile rows of the stride-2 N-split kernel for (clt, cht) accumulator tiles per wave on an LH-row map
 int ns_tile_rows(int clt, int cht, int LH) {
-  static const int tall = vts_tune("VTS_WGRAD_TALL", 1);
   // measured (tools/probes/wgrad_sweep.py): 8 rows help only with ONE high-resolution channel per wave (2 - 4 channel layers: up0
   // 52 -> 42 us, D layer 0 99 -> 77 us); with 2 - 3 channels per wave the 36 - 42 prefetch registers and 30 - 48 KB of patch rows
   // cost more co-resident workgroups than the longer tile saves (16 -> 8 channel layer: 43 -> 59 us)
-  if (!tall || cht != 1 || clt > 2 || LH < 64) return 2;
+  if (cht != 1 || clt > 2 || LH < 64) return 2;
   return 8;
 }
 
@@ -1277,7 +1274,7 @@ extern "C" int vts_wgrad_reduce_batch(const vts_reduce_job* jobs, int njobs, voi
       t.blk_start[j] = blocks;
       int maxpw = 0;
       for (int sg = 0; sg < q.nseg; ++sg) maxpw = q.pw[sg] > maxpw ? q.pw[sg] : maxpw;
-      static const int narrow_min = vts_tune("VTS_REDUCE_NARROW_MIN", 256);
+      constexpr int narrow_min = 256;                // (lane groups split the copies above it: step 6.47 -> 6.36 ms, round 3)
       t.narrow[j] = maxpw > narrow_min ? 1 : 0;      // more than 16 copies per wave of the 256-element form
       blocks += (int)cdiv64(q.nel, t.narrow[j] ? 64 : RB_ELEMS);
     }

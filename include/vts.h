@@ -825,6 +825,50 @@ int vts_allreduce_flat_async(void* comm, float* buf, int64_t n, void* producer_s
 int vts_allreduce_flat_wait(void* comm, void* consumer_stream);
 int vts_comm_destroy(void* comm);
 
+/* ---- SPADE generator (csrc/vts_spade.hip; reference models/networks.py:2075-2200 SPADEGenerator, models/architecture.py:21-68
+ * SPADEResnetBlock, models/normalization.py:68-112 SPADE).  The convolutions run on the entries above; these are the rest.  All fp32,
+ * fixed-order reductions (bitwise repeatable), no allocation, capturable.
+ *
+ * vts_spade_modulate (normalization.py:101-110, with the LeakyReLU(0.2) of architecture.py:53-54, 67-68 when act = VTS_ACT_LRELU):
+ *   out[n,c,y,x] = act((x - mean[n*C+c]) * rstd[n*C+c] * (1 + gamma[n,c,y,x]) + beta[n,c,y,x])
+ *   mean / rstd [N*C]: mean_out / rstd_out of vts_norm_stats (mode 0 = InstanceNorm2d(affine=False), mode 1 without gamma / beta =
+ *   BatchNorm2d(affine=False) in training mode, which also advances the running statistics), or the running statistics broadcast
+ *   over the batch (eval).  out_pad = 1: out is [N][C][H+2][W+2] with a zero border, the pre-padded operand of vts_conv3x3_wide.
+ * vts_spade_modulate_bwd: g = gradient of `out` ([N][C][H+2 g_pad][W+2 g_pad], read at its interior), g' = g * act'(.):
+ *   dgamma = g' * xhat,  dbeta = g'   (the output gradients of the gamma / beta convolutions),  h = g' * (1 + gamma)
+ *   mode 0 / 1 (statistics of this batch, instance / batch grouping):  dx = rstd * ((h - mean_G(h)) - (xhat - mean_G(xhat)) * mean_G(h * xhat))
+ *                                                                      (mean_G(xhat) = 0 exactly; the computed one keeps sum_G(dx) at rounding level)
+ *   mode 2 (frozen statistics, eval):                                  dx = rstd * h
+ *   ws: vts_spade_modulate_bwd_ws_floats(N, C) floats (plane sums, group means); may be NULL in mode 2.
+ * vts_nearest_resize: F.interpolate(mode="nearest") (networks.py:2149, normalization.py:104): out[.,oy,ox] = x[., sy(oy), sx(ox)],
+ *   s(d) = min(floor(d * in / out), in - 1) evaluated as ATen does (float scale; identity and exact halving as integer shortcuts).
+ *   _bwd: din (+)= the adjoint (each source pixel gathers the destinations that read it).
+ * vts_nearest_up2 / _bwd: nn.Upsample(scale_factor=2) (networks.py:2117) and its adjoint, the sum over each 2 x 2 cell.
+ * vts_spectral_norm: torch.nn.utils.spectral_norm (architecture.py:35-39) of W = w viewed [Co][K], K = Ci * kh * kw:
+ *   training != 0:  v <- W^T u / max(|W^T u|, eps);  u <- W v / max(|W v|, eps)   (one power iteration, stored in place)
+ *   always:         sigma[0] = u^T W v;  w_out = w / sigma.        ws: vts_spectral_norm_ws_floats(Co, K) floats.
+ * vts_spectral_norm_bwd: g = gradient of w_out;  dw (+)= (g - <g, w_sn> u v^T) / sigma  with u, v, sigma, w_sn as the forward left them
+ *   (u and v are constants of the backward, as in torch); ws: >= Co + 1 floats.
+ * vts_spade_eval_stats: mean[n*C+c] = running_mean[c], rstd[n*C+c] = 1 / sqrt(running_var[c] + eps): the eval-mode statistics of
+ *   BatchNorm2d(affine=False) in the layout vts_spade_modulate reads.
+ * vts_tanh_bwd: dz = g * (1 - y * y) for y = tanh(z), the generator's output activation (networks.py:2198), n elements. */
+int vts_spade_modulate(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int N, int C, int H, int W,
+                       int act, float* out, int out_pad, void* stream);
+int vts_spade_eval_stats(const float* running_mean, const float* running_var, float eps, int N, int C, float* mean, float* rstd, void* stream);
+int64_t vts_spade_modulate_bwd_ws_floats(int N, int C);
+int vts_spade_modulate_bwd(const float* g, int g_pad, const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                           int N, int C, int H, int W, int mode, int act, float* dgamma, float* dbeta, float* dx, float* ws, void* stream);
+int vts_tanh_bwd(const float* g, const float* y, int64_t n, float* dz, void* stream);
+int vts_nearest_resize(const float* x, int64_t NC, int IH, int IW, int OH, int OW, float* out, void* stream);
+int vts_nearest_resize_bwd(const float* dout, int64_t NC, int IH, int IW, int OH, int OW, float* din, int accumulate, void* stream);
+int vts_nearest_up2(const float* x, int64_t NC, int H, int W, float* out, void* stream);
+int vts_nearest_up2_bwd(const float* dout, int64_t NC, int H, int W, float* din, int accumulate, void* stream);
+int64_t vts_spectral_norm_ws_floats(int Co, int K);
+int vts_spectral_norm(const float* w, float* u, float* v, int Co, int K, int training, float eps, float* w_out, float* sigma, float* ws,
+                      int64_t ws_floats, void* stream);
+int vts_spectral_norm_bwd(const float* g, const float* w_sn, const float* u, const float* v, const float* sigma, int Co, int K, float* dw,
+                          int accumulate, float* ws, int64_t ws_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

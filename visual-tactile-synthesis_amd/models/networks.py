@@ -346,6 +346,136 @@ class GlobalGenerator(ResnetGenerator):
                          down="stride", up="convT", conv_bias=True, opt=opt)
 
 
+class _SNConvParams(_ConvParams):
+    """A convolution under torch.nn.utils.spectral_norm (reference models/architecture.py:35-39): the parameter is `weight_orig`, the power
+    iteration's vectors `weight_u` [Co] / `weight_v` [Ci k k] are buffers, drawn N(0, 1) and normalised as torch does; state-dict order as
+    torch leaves it (bias, weight_orig, weight_u, weight_v).  `weight` names the raw parameter, so init_weights draws `weight_orig` by
+    `init_type` like every other convolution.  (This departs from what the reference's code does on construction: there `weight` of a
+    spectral-normalised layer is a derived plain tensor, init_weights writes into that, and `weight_orig` keeps nn.Conv2d's default
+    initialisation.  A trained checkpoint overwrites either; a network trained from scratch starts from the draw named by `init_type`.)"""
+
+    def __init__(self, shape, bias_n):
+        nn.Module.__init__(self)
+        self.bias = nn.Parameter(torch.zeros(bias_n)) if bias_n else None
+        self.weight_orig = nn.Parameter(torch.zeros(shape))
+        co, k = shape[0], shape[1] * shape[2] * shape[3]
+        self.register_buffer("weight_u", nn.functional.normalize(torch.randn(co), dim=0, eps=1e-12))
+        self.register_buffer("weight_v", nn.functional.normalize(torch.randn(k), dim=0, eps=1e-12))
+        self.transposed = False
+
+    @property
+    def weight(self):
+        return self.weight_orig
+
+
+class _ParamFreeNorm(nn.Module):
+    """BatchNorm2d(affine=False) / SynchronizedBatchNorm2d(affine=False): running statistics only; InstanceNorm2d(affine=False): nothing"""
+
+    def __init__(self, kind, c):
+        super().__init__()
+        self.kind = kind
+        if kind != "instance":
+            self.register_buffer("running_mean", torch.zeros(c))
+            self.register_buffer("running_var", torch.ones(c))
+            self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
+
+
+class SPADE(nn.Module):
+    """Spatially-adaptive normalisation (reference models/normalization.py:68-112), config `spade<batch|syncbatch|instance>3x3`:
+    parameter-free norm of x, scale / shift maps convolved from the nearest-resized segmentation map (hidden width 128)."""
+
+    NHIDDEN = 128
+
+    def __init__(self, config_text, norm_nc, label_nc):
+        super().__init__()
+        # the format is spade<norm><k>x<k>: what stands between the prefix and the kernel size names the parameter-free normalisation
+        body = config_text[len("spade"):] if config_text.startswith("spade") else ""
+        size = body[-3:]
+        kind = body[:-3]
+        if len(size) != 3 or size[1] != "x" or not (size[0].isdigit() and size[2].isdigit()) or not kind:
+            raise ValueError("SPADE: config %r does not read spade<norm><k>x<k>" % config_text)
+        if kind not in ("instance", "syncbatch", "batch"):
+            raise ValueError("SPADE: parameter-free normalisation %r is not one of instance, syncbatch, batch" % kind)
+        if size != "3x3":
+            raise NotImplementedError("SPADE: kernel size %s is not built (3x3 only)" % size)
+        self.kind, self.norm_nc, self.label_nc = kind, norm_nc, label_nc
+        self.param_free_norm = _ParamFreeNorm(kind, norm_nc)
+        self.mlp_shared = _Holder({0: _ConvParams((self.NHIDDEN, label_nc, 3, 3), self.NHIDDEN)})
+        self.mlp_gamma = _ConvParams((norm_nc, self.NHIDDEN, 3, 3), norm_nc)
+        self.mlp_beta = _ConvParams((norm_nc, self.NHIDDEN, 3, 3), norm_nc)
+
+    def forward(self, x, segmap):
+        out, _ = engine.spade_norm_forward(self, x, segmap, keep=False)
+        return out
+
+
+class SPADEResnetBlock(nn.Module):
+    """reference models/architecture.py:21-68; opt supplies normG (a `spectral` prefix puts conv_0 / conv_1 / conv_s under spectral
+    normalisation) and semantic_nc"""
+
+    def __init__(self, fin, fout, opt):
+        super().__init__()
+        self.learned_shortcut = fin != fout
+        fmid = min(fin, fout)
+        self.spectral = "spectral" in opt.normG
+        conv = _SNConvParams if self.spectral else _ConvParams
+        self.conv_0 = conv((fmid, fin, 3, 3), fmid)
+        self.conv_1 = conv((fout, fmid, 3, 3), fout)
+        if self.learned_shortcut:
+            self.conv_s = conv((fout, fin, 1, 1), 0)
+        cfg = opt.normG.replace("spectral", "")
+        self.norm_0 = SPADE(cfg, fin, opt.semantic_nc)
+        self.norm_1 = SPADE(cfg, fmid, opt.semantic_nc)
+        if self.learned_shortcut:
+            self.norm_s = SPADE(cfg, fin, opt.semantic_nc)
+
+    def forward(self, x, seg):
+        out, _ = engine.spade_block_forward(self, x, seg, keep=False)
+        return out
+
+
+class SPADEGenerator(nn.Module):
+    """reference models/networks.py:2075-2200, the deterministic form (the latent is the downsampled segmentation map).  opt:
+    normG, semantic_nc, num_upsampling_layers (3 .. 7), output_width, aspect_ratio, use_vae (raises: ConvEncoder / the z path are not built)."""
+
+    def __init__(self, input_nc, output_nc, ngf, opt):
+        super().__init__()
+        if getattr(opt, "use_vae", False):
+            raise NotImplementedError("SPADEGenerator: --use_vae (the z-vector input and ConvEncoder) is not built")
+        L = int(opt.num_upsampling_layers)
+        if L < 3:
+            raise ValueError("SPADEGenerator: num_upsampling_layers %d < 3 leaves final_nc unbound in the reference (networks.py:2096-2115)" % L)
+        if L > 7:
+            raise ValueError("SPADEGenerator: num_upsampling_layers %d > 7 is not a reference configuration" % L)
+        self.num_upsampling_layers = L
+        nf = ngf
+        self.sw = opt.output_width // (2 ** L)
+        self.sh = round(self.sw / opt.aspect_ratio)
+        if self.sw < 1 or self.sh < 1:
+            raise ValueError("SPADEGenerator: output_width %d is too small for %d upsampling layers" % (opt.output_width, L))
+        self.fc = _ConvParams((16 * nf, input_nc, 3, 3), 16 * nf)
+        self.head_0 = SPADEResnetBlock(16 * nf, 16 * nf, opt)
+        self.G_middle_0 = SPADEResnetBlock(16 * nf, 16 * nf, opt)
+        self.G_middle_1 = SPADEResnetBlock(16 * nf, 16 * nf, opt)
+        self.up_0 = SPADEResnetBlock(16 * nf, 8 * nf, opt)
+        self.up_1 = SPADEResnetBlock(8 * nf, 4 * nf, opt)
+        final_nc = 4 * nf
+        if L >= 4:
+            self.up_2 = SPADEResnetBlock(4 * nf, 2 * nf, opt)
+            final_nc = 2 * nf
+        if L >= 5:
+            self.up_3 = SPADEResnetBlock(2 * nf, nf, opt)
+            final_nc = nf
+        if L > 6:
+            self.up_4 = SPADEResnetBlock(nf, nf // 2, opt)
+            final_nc = nf // 2
+        self.conv_img = _ConvParams((output_nc, final_nc, 3, 3), output_nc)
+
+    def forward(self, seg, z=None, verbose=False):
+        out, _ = engine.spade_forward(self, seg, keep=False)
+        return out
+
+
 def _patchgan_layout(n_layers):
     """Sequential indices of one NLayerDiscriminator (reference networks.py:1696-1737): conv 0 (stride 2); n_layers - 1 blocks
     [conv stride 2, norm, LeakyReLU]; one block [conv stride 1, norm, LeakyReLU]; conv stride 1 -> 1 channel."""
@@ -488,9 +618,17 @@ def define_G(input_nc, output_nc, ngf, netG, norm="batch", use_dropout=False, in
         net = StyleGAN2Generator(input_nc, output_nc, ngf, n_blocks=2 if netG == "smallstylegan2" else 6, size=size,
                                  num_downsampling=getattr(opt, "stylegan2_G_num_downsampling", 1), inject_noise="small" not in netG)
         return init_net(net, init_type, init_gain, gpu_ids, initialize_weights=False)
+    if netG == "spade":
+        # networks.py:314-315: SPADEGenerator(input_nc, output_nc, ngf, opt); the usual init_weights applies.  opt.semantic_nc is the
+        # channel count of the map the SPADE layers read (the generator's own input)
+        import argparse
+        o = argparse.Namespace(normG=getattr(opt, "normG", norm), semantic_nc=getattr(opt, "semantic_nc", None) or input_nc,
+                               num_upsampling_layers=getattr(opt, "num_upsampling_layers", 3), output_width=getattr(opt, "output_width", 32),
+                               aspect_ratio=getattr(opt, "aspect_ratio", 1.0), use_vae=getattr(opt, "use_vae", False))
+        return init_net(SPADEGenerator(input_nc, output_nc, ngf, o), init_type, init_gain, gpu_ids)
     if netG not in resnet_blocks and netG not in ("unet256_custom", "global", "local"):
         raise NotImplementedError("Generator model name [%s] is not recognized (built: unet256_custom, resnet_{4,6,9}blocks, global, local, "
-                                  "stylegan2, smallstylegan2)" % netG)
+                                  "stylegan2, smallstylegan2, spade)" % netG)
     if netG == "local":    # pix2pixHD LocalEnhancer (networks.py:311-313)
         if norm not in ("batch", "instance"):
             raise NotImplementedError("local enhancer: norm %s is not built" % norm)

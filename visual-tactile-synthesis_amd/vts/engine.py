@@ -2285,3 +2285,292 @@ def sifid_tactile(net, real_T, fake_T, size=299):
         b = ops.sifid_input(fake_T, c, 1, size=(size, size), clamp01=True)
         vals.append(sifid_pairs(net, a, b))
     return ((vals[0] + vals[1]) * 0.5).mean()
+
+
+# ======================================================================================================================
+# SPADE generator (`--netG spade`; reference models/networks.py:2075-2200, models/architecture.py:21-68, models/normalization.py:68-112)
+# Every 3x3 convolution reads a pre-padded operand (the modulate kernel stores that layout directly); layers of >= 64 x 64 channels
+# run on the GEMM-class kernels, the rest (label_nc = 1 inputs, the output_nc-channel image head, the 1x1 shortcut) on the 4x4 family.
+# ======================================================================================================================
+def _sp_wide(w):
+    co, ci, k = w.shape[0], w.shape[1], w.shape[2]
+    return k == 3 and co >= 64 and ci >= 64 and co % 4 == 0 and ci % 4 == 0
+
+
+def _sp_conv(p, w, b, out, act_out=0):
+    """out [N,Co,H,W] <- act_out(valid 3x3 convolution of the pre-padded p [N,Ci,H+2,W+2] + b)"""
+    if _sp_wide(w):
+        if act_out:
+            raise NotImplementedError("an output activation on the GEMM-class 3x3 convolution (an image head of >= 64 channels)")
+        return ops.conv3x3_wide(p, ops.w3x3_pack(w, "conv_fwd"), b, out)
+    co, ci = w.shape[:2]
+    w4 = ops.tap_embed(w, 3, 0, 0, ops._w4_scratch(w, 3, "fwd")[0])
+    return ops.conv4x4(p, w4, ci * 16, 16, co, out, bias=b, stride=1, pad=0, act_out=act_out)
+
+
+def _sp_conv_bwd_data(g, w, dp):
+    """dp [N,Ci,H+2,W+2] <- adjoint of _sp_conv w.r.t. its padded operand"""
+    if _sp_wide(w):
+        return ops.conv3x3_wide(ops.pad_affine(g, (2, 2, 2, 2), 0), ops.w3x3_pack(w, "conv_adj"), None, dp)
+    return ops.convk_bwd_data(g, w, dp, pad=0)
+
+
+def _sp_wgrad(g, p, dw):
+    if _sp_wide(dw):
+        return ops.wgrad3x3_wide(g, p, dw)
+    return ops.wgradk(g, p, dw, pad=0)
+
+
+class _SnState:
+    """what one spectral-normalised convolution keeps between the generator's forward and backward: W / sigma, sigma, a gradient buffer"""
+    __slots__ = ("w", "sigma", "g")
+
+
+def _sn_state(conv):
+    st = getattr(conv, "_sn_state", None)
+    w = conv.weight_orig
+    if st is None or st.w.shape != w.shape or st.w.device != w.device:
+        st = _SnState()
+        st.w, st.g, st.sigma = torch.empty_like(w), torch.empty_like(w), torch.empty(1, dtype=torch.float32, device=w.device)
+        object.__setattr__(conv, "_sn_state", st)
+    return st
+
+
+def _sn_convs(mod):
+    return [m for m in mod.modules() if hasattr(m, "weight_u")]
+
+
+def spectral_weights(mod, training):
+    """the spectral-norm forward of every such convolution below `mod`: one power iteration each in training (u / v advance in place),
+    W / sigma left in the convolution's state.  Runs once per forward of the network, not once per use of a weight."""
+    for conv in _sn_convs(mod):
+        st = _sn_state(conv)
+        ops.spectral_norm(conv.weight_orig, conv.weight_u, conv.weight_v, training, st.w, st.sigma)
+
+
+def _sp_weight(conv):
+    return _sn_state(conv).w if hasattr(conv, "weight_u") else conv.weight
+
+
+def _sp_param_grads(conv, g, p, k3=True):
+    """weight (+ bias) gradient of a block convolution from its output gradient g and its operand p"""
+    if conv.bias is not None:
+        ops.channel_sum(g, _grad(conv.bias))
+    sn = hasattr(conv, "weight_u")
+    dw = _sn_state(conv).g if sn else _grad(conv.weight)
+    if k3:
+        _sp_wgrad(g, p, dw)
+    else:
+        ops.wgradk(g, p, dw, pad=0)
+    if sn:
+        st = _sn_state(conv)
+        ops.spectral_norm_bwd(st.g, st.w, conv.weight_u, conv.weight_v, st.sigma, _grad(conv.weight_orig))
+
+
+class SpadeNormCtx:
+    __slots__ = ("x", "mean", "rstd", "gamma", "beta", "a_raw", "p_act", "s_pad", "mode", "act", "seg_shape")
+
+
+def _seg_at(seg, h, w, cache):
+    """zero-padded nearest resize of the segmentation map to h x w; one per resolution and network forward (cache)"""
+    key = (h, w)
+    if cache is not None and key in cache:
+        return cache[key]
+    s = seg if tuple(seg.shape[2:]) == (h, w) else ops.nearest_resize(seg, (h, w))
+    sp = ops.pad_affine(s, (1, 1, 1, 1), 0)
+    if cache is not None:
+        cache[key] = sp
+    return sp
+
+
+def spade_norm_forward(m, x, seg, act=0, out_pad=0, keep=True, cache=None, training=None):
+    """SPADE.forward (normalization.py:98-112) followed by `act` (0 | LRELU).  m: models.networks.SPADE.  Returns (out, ctx);
+    out_pad 1: out is the zero-bordered [N,C,H+2,W+2] operand of the next 3x3 convolution."""
+    n, c, h, w = x.shape
+    training = m.training if training is None else training
+    pf = m.param_free_norm
+    if pf.kind == "instance":
+        a, mode = ops.norm_stats(x, 0), 0
+        mean, rstd = a.mean, a.rstd
+    elif training:
+        # nn.BatchNorm2d counts its batches; SynchronizedBatchNorm2d's single-device path (F.batch_norm) leaves the counter alone
+        a, mode = ops.norm_stats(x, 1, running_mean=pf.running_mean, running_var=pf.running_var,
+                                 nbt=pf.num_batches_tracked if pf.kind == "batch" else None), 1
+        mean, rstd = a.mean, a.rstd
+    else:
+        mode = 2
+        mean, rstd = ops.spade_eval_stats(pf.running_mean, pf.running_var, n)
+    s_pad = _seg_at(seg, h, w, cache)
+    sh = getattr(m.mlp_shared, "0")
+    a_raw = _empty(n, m.NHIDDEN, h, w, x.device)
+    _sp_conv(s_pad, sh.weight, sh.bias, a_raw)
+    p_act = ops.pad_affine(a_raw, (1, 1, 1, 1), 0, act=RELU)
+    gamma, beta = _empty(n, c, h, w, x.device), _empty(n, c, h, w, x.device)
+    _sp_conv(p_act, m.mlp_gamma.weight, m.mlp_gamma.bias, gamma)
+    _sp_conv(p_act, m.mlp_beta.weight, m.mlp_beta.bias, beta)
+    out = ops.spade_modulate(x, mean, rstd, gamma, beta, act=act, out_pad=out_pad)
+    if not keep:
+        return out, None
+    ctx = SpadeNormCtx()
+    ctx.x, ctx.mean, ctx.rstd, ctx.gamma, ctx.beta, ctx.a_raw, ctx.p_act, ctx.s_pad = x, mean, rstd, gamma, beta, a_raw, p_act, s_pad
+    ctx.mode, ctx.act, ctx.seg_shape = mode, act, tuple(seg.shape)
+    return out, ctx
+
+
+def spade_norm_backward(m, ctx, g, g_pad=0, dsegs=None):
+    """g: gradient of spade_norm_forward's output (g_pad 1: in the padded layout).  Writes the six parameter gradients, returns
+    (dx, dseg).  dsegs: {(h, w): gradient w.r.t. the resized map}, the per-resolution accumulators of a network backward -- with it
+    dseg is None and the caller folds the accumulators back to the map's own size once (spade_dseg)."""
+    n, c, h, w = ctx.x.shape
+    dgamma, dbeta, dx = ops.spade_modulate_bwd(g, ctx.x, ctx.mean, ctx.rstd, ctx.gamma, ctx.beta, ctx.mode, act=ctx.act, g_pad=g_pad)
+    dev = dx.device
+    da_sum = _empty(n, m.NHIDDEN, h, w, dev)
+    for i, (conv, dmap) in enumerate(((m.mlp_gamma, dgamma), (m.mlp_beta, dbeta))):
+        ops.channel_sum(dmap, _grad(conv.bias))
+        _sp_wgrad(dmap, ctx.p_act, _grad(conv.weight))
+        dp = _sp_conv_bwd_data(dmap, conv.weight, _empty(n, m.NHIDDEN, h + 2, w + 2, dev))
+        ops.pad_bwd(dp, (1, 1, 1, 1), 0, da_sum, accumulate=i > 0)
+    da = _empty(n, m.NHIDDEN, h, w, dev)
+    ops.act_bwd(da_sum, ctx.a_raw, RELU, da)
+    sh = getattr(m.mlp_shared, "0")
+    ops.channel_sum(da, _grad(sh.bias))
+    _sp_wgrad(da, ctx.s_pad, _grad(sh.weight))
+    dsp = _sp_conv_bwd_data(da, sh.weight, _empty(n, ctx.seg_shape[1], h + 2, w + 2, dev))
+    own = dsegs is None
+    if own:
+        dsegs = {}
+    acc = dsegs.get((h, w))
+    if acc is None:
+        dsegs[(h, w)] = ops.pad_bwd(dsp, (1, 1, 1, 1), 0, _empty(n, ctx.seg_shape[1], h, w, dev))
+    else:
+        ops.pad_bwd(dsp, (1, 1, 1, 1), 0, acc, accumulate=True)
+    return dx, (spade_dseg(dsegs, ctx.seg_shape, dev) if own else None)
+
+
+def spade_dseg(dsegs, seg_shape, dev):
+    """fold the per-resolution gradients of the resized maps back onto the segmentation map (adjoint of the nearest resizes)"""
+    dseg = torch.empty(seg_shape, dtype=torch.float32, device=dev)
+    for i, key in enumerate(sorted(dsegs)):
+        ops.nearest_resize_bwd(dsegs[key], dseg, accumulate=i > 0)
+    return dseg
+
+
+class SpadeBlockCtx:
+    __slots__ = ("n0", "p0", "n1", "p1", "ns", "ps", "x_shape")
+
+
+def spade_block_forward(blk, x, seg, keep=True, cache=None, weights_ready=False):
+    """SPADEResnetBlock.forward (architecture.py:50-68).  weights_ready: the caller already ran spectral_weights for this forward."""
+    if not weights_ready:
+        spectral_weights(blk, blk.training)
+    n, fin, h, w = x.shape
+    dev = x.device
+    ctx = SpadeBlockCtx()
+    ctx.x_shape = tuple(x.shape)
+    if blk.learned_shortcut:
+        ws = _sp_weight(blk.conv_s)
+        ctx.ps, ctx.ns = spade_norm_forward(blk.norm_s, x, seg, act=0, out_pad=0, keep=keep, cache=cache, training=blk.training)
+        x_s = ops.convk(ctx.ps, ws, _empty(n, ws.shape[0], h, w, dev), pad=0)
+    else:
+        x_s = x
+    w0, w1 = _sp_weight(blk.conv_0), _sp_weight(blk.conv_1)
+    ctx.p0, ctx.n0 = spade_norm_forward(blk.norm_0, x, seg, act=LRELU, out_pad=1, keep=keep, cache=cache, training=blk.training)
+    d0 = _sp_conv(ctx.p0, w0, blk.conv_0.bias, _empty(n, w0.shape[0], h, w, dev))
+    ctx.p1, ctx.n1 = spade_norm_forward(blk.norm_1, d0, seg, act=LRELU, out_pad=1, keep=keep, cache=cache, training=blk.training)
+    d1 = _sp_conv(ctx.p1, w1, blk.conv_1.bias, _empty(n, w1.shape[0], h, w, dev))
+    out = ops.pad_affine(d1, (0, 0, 0, 0), 0, res=x_s)
+    return out, (ctx if keep else None)
+
+
+def spade_block_backward(blk, ctx, g, dsegs=None):
+    """g: gradient of the block's output.  Parameter gradients into .grad (overwritten); returns (dx, dseg) -- dseg as spade_norm_backward"""
+    g = g.contiguous()
+    n, fin, h, w = ctx.x_shape
+    dev = g.device
+    own = dsegs is None
+    if own:
+        dsegs = {}
+    w0, w1 = _sp_weight(blk.conv_0), _sp_weight(blk.conv_1)
+    _sp_param_grads(blk.conv_1, g, ctx.p1)
+    dp1 = _sp_conv_bwd_data(g, w1, _empty(n, w1.shape[1], h + 2, w + 2, dev))
+    dd0, _ = spade_norm_backward(blk.norm_1, ctx.n1, dp1, g_pad=1, dsegs=dsegs)
+    _sp_param_grads(blk.conv_0, dd0, ctx.p0)
+    dp0 = _sp_conv_bwd_data(dd0, w0, _empty(n, fin, h + 2, w + 2, dev))
+    dx, _ = spade_norm_backward(blk.norm_0, ctx.n0, dp0, g_pad=1, dsegs=dsegs)
+    if blk.learned_shortcut:
+        ws = _sp_weight(blk.conv_s)
+        _sp_param_grads(blk.conv_s, g, ctx.ps, k3=False)
+        dps = ops.convk_bwd_data(g, ws, _empty(n, fin, h, w, dev), pad=0)
+        dxs, _ = spade_norm_backward(blk.norm_s, ctx.ns, dps, g_pad=0, dsegs=dsegs)
+    else:
+        dxs = g
+    dx = ops.pad_affine(dx, (0, 0, 0, 0), 0, res=dxs)
+    seg_shape = ctx.n0.seg_shape
+    return dx, (spade_dseg(dsegs, seg_shape, dev) if own else None)
+
+
+class SpadeCtx:
+    __slots__ = ("seg_shape", "s0_pad", "blocks", "x_last", "p_last", "out")
+
+
+def _spade_plan(G):
+    """(block, upsample in front of it) in forward order behind head_0 (networks.py:2153-2193)"""
+    L = G.num_upsampling_layers
+    plan = [(G.head_0, 0), (G.G_middle_0, 1), (G.G_middle_1, 1 if L > 5 else 0), (G.up_0, 1), (G.up_1, 1)]
+    if L > 3:
+        plan.append((G.up_2, 1))
+    if L > 4:
+        plan.append((G.up_3, 1))
+    if L > 6:
+        plan.append((G.up_4, 1))
+    return plan
+
+
+def spade_forward(G, seg, keep=True):
+    """SPADEGenerator.forward (networks.py:2135-2200) of the segmentation map seg [N, input_nc, H, W] -> ([N, output_nc, H', W'], ctx)"""
+    seg = seg.contiguous()
+    n, dev = seg.shape[0], seg.device
+    spectral_weights(G, G.training)
+    cache = {}
+    ctx = SpadeCtx()
+    ctx.seg_shape = tuple(seg.shape)
+    ctx.s0_pad = _seg_at(seg, G.sh, G.sw, cache)
+    x = _sp_conv(ctx.s0_pad, G.fc.weight, G.fc.bias, _empty(n, G.fc.weight.shape[0], G.sh, G.sw, dev))
+    ctx.blocks = []
+    for blk, up in _spade_plan(G):
+        if up:
+            x = ops.nearest_up2(x)
+        x, bctx = spade_block_forward(blk, x, seg, keep=keep, cache=cache, weights_ready=True)
+        ctx.blocks.append(bctx)
+    ctx.x_last = x
+    ctx.p_last = ops.pad_affine(x, (1, 1, 1, 1), 0, act=LRELU)
+    out = _sp_conv(ctx.p_last, G.conv_img.weight, G.conv_img.bias, _empty(n, G.conv_img.weight.shape[0], x.shape[2], x.shape[3], dev), act_out=TANH)
+    ctx.out = out
+    return out, (ctx if keep else None)
+
+
+def spade_backward(G, ctx, dout):
+    """dout: gradient of the generator's (post-tanh) output.  Every parameter's .grad is overwritten; returns dseg."""
+    dev = dout.device
+    n = dout.shape[0]
+    x = ctx.x_last
+    dz = ops.tanh_bwd(dout.contiguous(), ctx.out)
+    ops.channel_sum(dz, _grad(G.conv_img.bias))
+    _sp_wgrad(dz, ctx.p_last, _grad(G.conv_img.weight))
+    dp = _sp_conv_bwd_data(dz, G.conv_img.weight, _empty(n, x.shape[1], x.shape[2] + 2, x.shape[3] + 2, dev))
+    gc = ops.pad_bwd(dp, (1, 1, 1, 1), 0, torch.empty_like(x))
+    g = ops.act_bwd(gc, x, LRELU, torch.empty_like(x))
+    dsegs = {}
+    for (blk, up), bctx in zip(reversed(_spade_plan(G)), reversed(ctx.blocks)):
+        g, _ = spade_block_backward(blk, bctx, g, dsegs=dsegs)
+        if up:
+            g = ops.nearest_up2_bwd(g)
+    ops.channel_sum(g, _grad(G.fc.bias))
+    _sp_wgrad(g, ctx.s0_pad, _grad(G.fc.weight))
+    ds0 = _sp_conv_bwd_data(g, G.fc.weight, _empty(n, ctx.seg_shape[1], G.sh + 2, G.sw + 2, dev))
+    acc = dsegs.get((G.sh, G.sw))
+    if acc is None:
+        dsegs[(G.sh, G.sw)] = ops.pad_bwd(ds0, (1, 1, 1, 1), 0, _empty(n, ctx.seg_shape[1], G.sh, G.sw, dev))
+    else:
+        ops.pad_bwd(ds0, (1, 1, 1, 1), 0, acc, accumulate=True)
+    return spade_dseg(dsegs, ctx.seg_shape, dev)

@@ -156,6 +156,8 @@ SYMBOLS = [
     "vts_maxpool2_relu_pad", "vts_maxpool3s2_relu_pad", "vts_s2d4_pad", "vts_maxpool2_relu_bwd", "vts_relu_mask_pad", "vts_lpips_layer", "vts_l1_relu", "vts_lpips_input", "vts_lpips_input_bwd",
     "vts_patch_jobs", "vts_g_post_stack", "vts_step_begin", "vts_conv4x4_bsums", "vts_norm_bwd_from_partials",
     "vts_u8_expand", "vts_unet_forward", "vts_unet_forward_ws_floats", "vts_patchgan_forward", "vts_patchgan_forward_ws_floats", "vts_msd_forward", "vts_msd_forward_ws_floats", "vts_unet_backward", "vts_unet_backward_ws_floats", "vts_patchgan_backward", "vts_patchgan_backward_ws_floats", "vts_msd_backward", "vts_msd_backward_ws_floats", "vts_allreduce_slice_plan", "vts_comm_unique_id", "vts_comm_init", "vts_allreduce_flat_async", "vts_allreduce_flat_wait", "vts_comm_destroy",
+    "vts_spade_modulate", "vts_spade_modulate_bwd_ws_floats", "vts_spade_modulate_bwd", "vts_nearest_resize", "vts_nearest_resize_bwd", "vts_nearest_up2", "vts_nearest_up2_bwd",
+    "vts_spectral_norm_ws_floats", "vts_spectral_norm", "vts_spectral_norm_bwd", "vts_tanh_bwd", "vts_spade_eval_stats",
 ]
 
 
@@ -209,6 +211,10 @@ def load():
     lib.vts_channel_sum_ws_floats.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.vts_modconv_scale_dot_ws_floats.argtypes = [C.c_int, C.c_int64]
     lib.vts_modconv_scale_dot_ws_floats.restype = C.c_int64
+    lib.vts_spade_modulate_bwd_ws_floats.argtypes = [C.c_int, C.c_int]
+    lib.vts_spade_modulate_bwd_ws_floats.restype = C.c_int64
+    lib.vts_spectral_norm_ws_floats.argtypes = [C.c_int, C.c_int]
+    lib.vts_spectral_norm_ws_floats.restype = C.c_int64
     vp, i, i64, f = C.c_void_p, C.c_int, C.c_int64, C.c_float
     sig = {
         "vts_conv4x4": [C.POINTER(ConvDesc), vp],
@@ -307,6 +313,14 @@ def load():
         "vts_l1_relu": [vp, vp, i64, f, vp, vp, vp],
         "vts_lpips_input": [vp, i64, i, i, i, c_f32p, c_f32p, vp, vp],
         "vts_lpips_input_bwd": [vp, i, i, i, c_f32p, vp, i64, i, vp],
+        "vts_spade_modulate": [vp, vp, vp, vp, vp, i, i, i, i, i, vp, i, vp],
+        "vts_spade_modulate_bwd": [vp, i, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp, vp, vp, vp, vp],
+        "vts_nearest_resize": [vp, i64, i, i, i, i, vp, vp], "vts_nearest_resize_bwd": [vp, i64, i, i, i, i, vp, i, vp],
+        "vts_nearest_up2": [vp, i64, i, i, vp, vp], "vts_nearest_up2_bwd": [vp, i64, i, i, vp, i, vp],
+        "vts_tanh_bwd": [vp, vp, i64, vp, vp],
+        "vts_spade_eval_stats": [vp, vp, f, i, i, vp, vp, vp],
+        "vts_spectral_norm": [vp, vp, vp, i, i, i, f, vp, vp, vp, i64, vp],
+        "vts_spectral_norm_bwd": [vp, vp, vp, vp, vp, i, i, vp, i, vp, i64, vp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)

@@ -1577,3 +1577,113 @@ def lpips_input_bwd(g, scale, dx, cx, accumulate=False, nstride=None):
     L.check(L.load().vts_lpips_input_bwd(g.data_ptr(), n, cx, h * w, _triple(scale), dx.data_ptr(), dx.stride(0) if nstride is None else nstride, int(accumulate),
                                          L.stream()), "vts_lpips_input_bwd")
     return dx
+
+
+# ---- SPADE generator (include/vts.h; reference models/normalization.py:68-112, models/architecture.py:21-68, models/networks.py:2075-2200) ----
+def spade_modulate(x, mean, rstd, gamma, beta, act=0, out_pad=0, out=None):
+    """out = act(xhat (1 + gamma) + beta), xhat = (x - mean[n,c]) rstd[n,c]; out_pad 1: the zero-bordered [H+2][W+2] layout of the 3x3 GEMM-class
+    convolution's operand"""
+    n, c, h, w = x.shape
+    if out is None:
+        out = torch.empty(n, c, h + 2 * out_pad, w + 2 * out_pad, dtype=torch.float32, device=x.device)
+    assert out.shape == (n, c, h + 2 * out_pad, w + 2 * out_pad) and gamma.shape == x.shape and beta.shape == x.shape
+    assert all(t.is_contiguous() for t in (x, gamma, beta, out)) and mean.numel() == n * c and rstd.numel() == n * c
+    _run("spade_modulate", 4.0 * (3 * x.numel() + out.numel()), 0.0, L.load().vts_spade_modulate, x.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+         gamma.data_ptr(), beta.data_ptr(), n, c, h, w, act, out.data_ptr(), out_pad, L.stream())
+    return out
+
+
+def spade_modulate_bwd(g, x, mean, rstd, gamma, beta, mode, act=0, g_pad=0):
+    """(dgamma, dbeta, dx) of spade_modulate; g: gradient of its output (g_pad 1: [H+2][W+2], read at its interior);
+    mode 0 instance / 1 batch statistics of this batch, 2 frozen (eval) statistics"""
+    n, c, h, w = x.shape
+    assert g.shape == (n, c, h + 2 * g_pad, w + 2 * g_pad) and all(t.is_contiguous() for t in (g, x, gamma, beta))
+    lib = L.load()
+    dgamma, dbeta, dx = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+    ws = workspace(lib.vts_spade_modulate_bwd_ws_floats(n, c), x.device)
+    _run("spade_modulate_bwd", 4.0 * x.numel() * (10 if mode != 2 else 7), 0.0, lib.vts_spade_modulate_bwd, g.data_ptr(), g_pad, x.data_ptr(),
+         mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), n, c, h, w, mode, act, dgamma.data_ptr(), dbeta.data_ptr(),
+         dx.data_ptr(), ws.data_ptr(), L.stream())
+    return dgamma, dbeta, dx
+
+
+def nearest_resize(x, size, out=None):
+    """F.interpolate(x, size, mode="nearest")"""
+    n, c, h, w = x.shape
+    oh, ow = size
+    if out is None:
+        out = torch.empty(n, c, oh, ow, dtype=torch.float32, device=x.device)
+    assert x.is_contiguous() and out.is_contiguous() and out.shape == (n, c, oh, ow)
+    _run("nearest_resize", 8.0 * out.numel(), 0.0, L.load().vts_nearest_resize, x.data_ptr(), n * c, h, w, oh, ow, out.data_ptr(), L.stream())
+    return out
+
+
+def nearest_resize_bwd(dout, din, accumulate=False):
+    """din [N,C,IH,IW] (+)= adjoint of nearest_resize(., dout's size) applied to dout"""
+    n, c, h, w = din.shape
+    assert dout.is_contiguous() and din.is_contiguous() and dout.shape[:2] == din.shape[:2]
+    _run("nearest_resize_bwd", 4.0 * (dout.numel() + din.numel()), 0.0, L.load().vts_nearest_resize_bwd, dout.data_ptr(), n * c, h, w,
+         dout.shape[2], dout.shape[3], din.data_ptr(), int(accumulate), L.stream())
+    return din
+
+
+def nearest_up2(x, out=None):
+    """nn.Upsample(scale_factor=2) (nearest)"""
+    n, c, h, w = x.shape
+    if out is None:
+        out = torch.empty(n, c, 2 * h, 2 * w, dtype=torch.float32, device=x.device)
+    assert x.is_contiguous() and out.is_contiguous() and out.shape == (n, c, 2 * h, 2 * w)
+    _run("nearest_up2", 20.0 * x.numel(), 0.0, L.load().vts_nearest_up2, x.data_ptr(), n * c, h, w, out.data_ptr(), L.stream())
+    return out
+
+
+def nearest_up2_bwd(dout, din=None, accumulate=False):
+    """din [N,C,H,W] (+)= sum over the 2 x 2 cells of dout [N,C,2H,2W]"""
+    n, c, h2, w2 = dout.shape
+    if din is None:
+        din = torch.empty(n, c, h2 // 2, w2 // 2, dtype=torch.float32, device=dout.device)
+    assert dout.is_contiguous() and din.is_contiguous() and dout.shape == (n, c, 2 * din.shape[2], 2 * din.shape[3])
+    _run("nearest_up2_bwd", 20.0 * din.numel(), 0.0, L.load().vts_nearest_up2_bwd, dout.data_ptr(), n * c, din.shape[2], din.shape[3],
+         din.data_ptr(), int(accumulate), L.stream())
+    return din
+
+
+def spectral_norm(w, u, v, training, w_out, sigma, eps=1e-12):
+    """torch.nn.utils.spectral_norm of w [Co, ...]: training: one power iteration, u / v updated in place; sigma[0] = u^T W v; w_out = w / sigma"""
+    co = w.shape[0]
+    k = w.numel() // co
+    assert u.numel() == co and v.numel() == k and w_out.numel() == w.numel() and all(t.is_contiguous() for t in (w, u, v, w_out, sigma))
+    lib = L.load()
+    ws = workspace(lib.vts_spectral_norm_ws_floats(co, k), w.device)
+    _run("spectral_norm", 4.0 * w.numel() * (4 if training else 3), 2.0 * w.numel() * (3 if training else 2), lib.vts_spectral_norm, w.data_ptr(),
+         u.data_ptr(), v.data_ptr(), co, k, int(training), eps, w_out.data_ptr(), sigma.data_ptr(), ws.data_ptr(), ws.numel(), L.stream())
+    return w_out
+
+
+def spectral_norm_bwd(g, w_sn, u, v, sigma, dw, accumulate=False):
+    """dw (+)= (g - <g, w_sn> u v^T) / sigma: the gradient of w through w / sigma(w) with u, v constant"""
+    co = g.shape[0]
+    k = g.numel() // co
+    assert all(t.is_contiguous() for t in (g, w_sn, u, v, dw)) and dw.numel() == g.numel() == w_sn.numel()
+    ws = workspace(co + 1, g.device)
+    _run("spectral_norm_bwd", 4.0 * g.numel() * (5 if accumulate else 4), 4.0 * g.numel(), L.load().vts_spectral_norm_bwd, g.data_ptr(), w_sn.data_ptr(),
+         u.data_ptr(), v.data_ptr(), sigma.data_ptr(), co, k, dw.data_ptr(), int(accumulate), ws.data_ptr(), ws.numel(), L.stream())
+    return dw
+
+
+def tanh_bwd(g, y, dz=None):
+    """dz = g (1 - y^2) for y = tanh(z)"""
+    if dz is None:
+        dz = torch.empty_like(y)
+    assert g.is_contiguous() and y.is_contiguous() and g.shape == y.shape
+    _run("tanh_bwd", 12.0 * y.numel(), 0.0, L.load().vts_tanh_bwd, g.data_ptr(), y.data_ptr(), y.numel(), dz.data_ptr(), L.stream())
+    return dz
+
+
+def spade_eval_stats(running_mean, running_var, n, eps=1e-5):
+    """(mean, rstd) [N*C] of BatchNorm2d(affine=False) in eval mode, in the layout spade_modulate reads"""
+    c = running_mean.numel()
+    st = torch.empty(2, n * c, dtype=torch.float32, device=running_mean.device)
+    _run("spade_eval_stats", 8.0 * (n + 1) * c, 0.0, L.load().vts_spade_eval_stats, running_mean.data_ptr(), running_var.data_ptr(), eps, n, c,
+         st[0].data_ptr(), st[1].data_ptr(), L.stream())
+    return st[0], st[1]

@@ -509,6 +509,15 @@ int vts_l1_relu(const float* za, const float* zb, int64_t n, float coeff, int64_
  * are HOST triples.  vts_lpips_input_bwd: dx (+)= adjoint applied to g [N][3][HW] */
 int vts_lpips_input(const float* x, int64_t x_nstride, int N, int Cx, int HW, const float* shift3, const float* scale3, float* y, void* stream);
 int vts_lpips_input_bwd(const float* g, int N, int Cx, int HW, const float* scale3, float* dx, int64_t dx_nstride, int accumulate, void* stream);
+/* The three VGG feature terms of a step (image, gx and gy each tiled to three channels) as ONE batch.  vts_vgg_stack_input: out
+ * [6 N][3][H + 2][W + 2], the stem's operand with a zero border, row groups fake_I, fake_gx x 3, fake_gy x 3, real_I, real_gx x 3,
+ * real_gy x 3; the images are [N][3][H][W], the tactile tensors [N][2][H][W] (gx, gy = channels 0, 1), each with its batch stride in
+ * floats (channel views of wider tensors).  vts_vgg_stack_input_bwd: the adjoint on the 3 N fake rows, dx [3 N][3][H][W]:
+ * d_fake_I (+)= dx[0:N]; d_fake_T[:, c] (+)= (dx[(1 + c) N + n][0] + dx[..][1]) + dx[..][2]; accumulate: add to / overwrite both */
+int vts_vgg_stack_input(const float* fake_I, int64_t fake_I_nstride, const float* real_I, int64_t real_I_nstride, const float* fake_T,
+                        int64_t fake_T_nstride, const float* real_T, int64_t real_T_nstride, int N, int H, int W, float* out, void* stream);
+int vts_vgg_stack_input_bwd(const float* dx, int N, int H, int W, float* d_fake_I, int64_t d_fake_I_nstride, float* d_fake_T,
+                            int64_t d_fake_T_nstride, int accumulate, void* stream);
 
 /* Start of a training step: loss slots <- 0, every optimiser's device step counter += 1 (vts_adam_flat_dev reads them): one launch */
 int vts_step_begin(int64_t* loss_slots, int nslots, int* step_counters, int ncounters, void* stream);

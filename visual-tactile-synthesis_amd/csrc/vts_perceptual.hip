@@ -362,6 +362,67 @@ __global__ __launch_bounds__(256) void lpips_input_kernel(const float* __restric
   }
 }
 
+// The VGG feature term of the SPADE / pix2pixHD step as ONE batch: the stem's zero-bordered operand [6 N][3][H + 2][W + 2] with the row
+// groups fake_I, fake_gx x 3, fake_gy x 3, real_I, real_gx x 3, real_gy x 3 (group g = row / N; gx / gy = channels 0 / 1 of the
+// tactile tensors, tiled to three channels).  One thread per output element, border included.
+__global__ __launch_bounds__(256) void vgg_stack_input_kernel(const float* __restrict__ fake_I, int64_t fI_ns, const float* __restrict__ real_I, int64_t rI_ns,
+                                                              const float* __restrict__ fake_T, int64_t fT_ns, const float* __restrict__ real_T, int64_t rT_ns,
+                                                              int N, int H, int W, float* __restrict__ out) {
+  const int row = blockIdx.y, grp = row / N, n = row - grp * N;
+  const int PH = H + 2, PW = W + 2, HW = H * W;
+  const int t = grp % 3;                       // 0: the image, 1 / 2: tactile channel 0 / 1
+  const float* src = grp < 3 ? (t == 0 ? fake_I + n * fI_ns : fake_T + n * fT_ns + (int64_t)(t - 1) * HW)
+                             : (t == 0 ? real_I + n * rI_ns : real_T + n * rT_ns + (int64_t)(t - 1) * HW);
+  float* o = out + (int64_t)row * 3 * PH * PW;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < 3 * PH * PW; i += gridDim.x * 256) {
+    const int c = i / (PH * PW), r = i - c * PH * PW, py = r / PW, px = r - py * PW;
+    const bool in = py >= 1 && py <= H && px >= 1 && px <= W;
+    o[i] = in ? src[(t == 0 ? (int64_t)c * HW : 0) + (py - 1) * W + (px - 1)] : 0.f;
+  }
+}
+
+// adjoint of the fake rows of vgg_stack_input: dx [3 N][3][HW] -> d_fake_I [N][3][HW] (one to one) and d_fake_T [N][2][HW] (the sum of the
+// three tiles, added as (c0 + c1) + c2).  V = 4: float4 accesses (HW, the batch strides and the pointers are multiples of 4 floats).
+template <int V>
+__global__ __launch_bounds__(256) void vgg_stack_input_bwd_kernel(const float* __restrict__ dx, int N, int HW, float* __restrict__ dI, int64_t dI_ns,
+                                                                  float* __restrict__ dT, int64_t dT_ns, int accumulate) {
+  const int n = blockIdx.y;
+  const float* gI = dx + (int64_t)n * 3 * HW;
+  float* oI = dI + n * dI_ns;
+  float* oT = dT + n * dT_ns;
+  for (int i = (blockIdx.x * 256 + threadIdx.x) * V; i < HW; i += gridDim.x * 256 * V) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (V == 4) {
+        float4 g = *reinterpret_cast<const float4*>(gI + (int64_t)c * HW + i);
+        float4* p = reinterpret_cast<float4*>(oI + (int64_t)c * HW + i);
+        if (accumulate) { const float4 a = *p; g.x += a.x; g.y += a.y; g.z += a.z; g.w += a.w; }
+        *p = g;
+      } else {
+        const float g = gI[(int64_t)c * HW + i];
+        float* p = oI + (int64_t)c * HW + i;
+        *p = accumulate ? *p + g : g;
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const float* gT = dx + ((int64_t)(1 + c) * N + n) * 3 * HW;
+      if (V == 4) {
+        const float4 a = *reinterpret_cast<const float4*>(gT + i), b = *reinterpret_cast<const float4*>(gT + HW + i),
+                     d = *reinterpret_cast<const float4*>(gT + 2 * (int64_t)HW + i);
+        float4 g = make_float4((a.x + b.x) + d.x, (a.y + b.y) + d.y, (a.z + b.z) + d.z, (a.w + b.w) + d.w);
+        float4* p = reinterpret_cast<float4*>(oT + (int64_t)c * HW + i);
+        if (accumulate) { const float4 e = *p; g.x += e.x; g.y += e.y; g.z += e.z; g.w += e.w; }
+        *p = g;
+      } else {
+        const float g = (gT[i] + gT[HW + i]) + gT[2 * (int64_t)HW + i];
+        float* p = oT + (int64_t)c * HW + i;
+        *p = accumulate ? *p + g : g;
+      }
+    }
+  }
+}
+
 inline unsigned blocks_1d(int64_t n) {
   const int64_t b = (n + 255) / 256;
   return (unsigned)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
@@ -470,5 +531,37 @@ extern "C" int vts_lpips_input_bwd(const float* g, int N, int Cx, int HW, const 
   hipLaunchKernelGGL(lpips_input_bwd_kernel, dim3(blocks_1d(HW), N), dim3(256), 0, (hipStream_t)stream, g, HW, Cx, 1.f / scale3[0], 1.f / scale3[1],
                      1.f / scale3[2], dx, dx_nstride, accumulate);
   VTS_CHECK_LAUNCH("vts_lpips_input_bwd");
+  return VTS_OK;
+}
+
+extern "C" int vts_vgg_stack_input(const float* fake_I, int64_t fake_I_nstride, const float* real_I, int64_t real_I_nstride, const float* fake_T,
+                                   int64_t fake_T_nstride, const float* real_T, int64_t real_T_nstride, int N, int H, int W, float* out, void* stream) {
+  VTS_CHECK_ARG(fake_I && real_I && fake_T && real_T && out && N >= 1 && 6 * (int64_t)N <= 65535 && H >= 1 && W >= 1 &&
+                    3 * ((int64_t)H + 2) * ((int64_t)W + 2) <= 0x7fffffff,
+                "vts_vgg_stack_input: bad args");
+  const int64_t hw = (int64_t)H * W;
+  VTS_CHECK_ARG(fake_I_nstride >= 3 * hw && real_I_nstride >= 3 * hw && fake_T_nstride >= 2 * hw && real_T_nstride >= 2 * hw,
+                "vts_vgg_stack_input: a batch stride is smaller than the channels read (3 H W of the images, 2 H W of the tactile tensors)");
+  hipLaunchKernelGGL(vgg_stack_input_kernel, dim3(blocks_1d(3 * ((int64_t)H + 2) * (W + 2)), 6 * N), dim3(256), 0, (hipStream_t)stream, fake_I, fake_I_nstride,
+                     real_I, real_I_nstride, fake_T, fake_T_nstride, real_T, real_T_nstride, N, H, W, out);
+  VTS_CHECK_LAUNCH("vts_vgg_stack_input");
+  return VTS_OK;
+}
+
+extern "C" int vts_vgg_stack_input_bwd(const float* dx, int N, int H, int W, float* d_fake_I, int64_t d_fake_I_nstride, float* d_fake_T,
+                                       int64_t d_fake_T_nstride, int accumulate, void* stream) {
+  VTS_CHECK_ARG(dx && d_fake_I && d_fake_T && N >= 1 && N <= 65535 && H >= 1 && W >= 1 && (int64_t)H * W <= 0x7fffffff / 4, "vts_vgg_stack_input_bwd: bad args");
+  const int HW = H * W;
+  VTS_CHECK_ARG(d_fake_I_nstride >= 3 * (int64_t)HW && d_fake_T_nstride >= 2 * (int64_t)HW,
+                "vts_vgg_stack_input_bwd: a batch stride is smaller than the channels written");
+  const bool v4 = HW % 4 == 0 && d_fake_I_nstride % 4 == 0 && d_fake_T_nstride % 4 == 0 &&
+                  ((reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(d_fake_I) | reinterpret_cast<uintptr_t>(d_fake_T)) & 15) == 0;
+  if (v4)
+    hipLaunchKernelGGL(vgg_stack_input_bwd_kernel<4>, dim3(blocks_1d(HW / 4), N), dim3(256), 0, (hipStream_t)stream, dx, N, HW, d_fake_I, d_fake_I_nstride,
+                       d_fake_T, d_fake_T_nstride, accumulate);
+  else
+    hipLaunchKernelGGL(vgg_stack_input_bwd_kernel<1>, dim3(blocks_1d(HW), N), dim3(256), 0, (hipStream_t)stream, dx, N, HW, d_fake_I, d_fake_I_nstride,
+                       d_fake_T, d_fake_T_nstride, accumulate);
+  VTS_CHECK_LAUNCH("vts_vgg_stack_input_bwd");
   return VTS_OK;
 }

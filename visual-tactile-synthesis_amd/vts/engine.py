@@ -2417,10 +2417,11 @@ def spade_norm_forward(m, x, seg, act=0, out_pad=0, keep=True, cache=None, train
     return out, ctx
 
 
-def spade_norm_backward(m, ctx, g, g_pad=0, dsegs=None):
+def spade_norm_backward(m, ctx, g, g_pad=0, dsegs=None, want_dseg=True):
     """g: gradient of spade_norm_forward's output (g_pad 1: in the padded layout).  Writes the six parameter gradients, returns
     (dx, dseg).  dsegs: {(h, w): gradient w.r.t. the resized map}, the per-resolution accumulators of a network backward -- with it
-    dseg is None and the caller folds the accumulators back to the map's own size once (spade_dseg)."""
+    dseg is None and the caller folds the accumulators back to the map's own size once (spade_dseg).  want_dseg False: nobody reads the
+    map's gradient (a training step: the sketch is data), so mlp_shared's input adjoint is not run and dseg is None."""
     n, c, h, w = ctx.x.shape
     dgamma, dbeta, dx = ops.spade_modulate_bwd(g, ctx.x, ctx.mean, ctx.rstd, ctx.gamma, ctx.beta, ctx.mode, act=ctx.act, g_pad=g_pad)
     dev = dx.device
@@ -2435,6 +2436,8 @@ def spade_norm_backward(m, ctx, g, g_pad=0, dsegs=None):
     sh = getattr(m.mlp_shared, "0")
     ops.channel_sum(da, _grad(sh.bias))
     _sp_wgrad(da, ctx.s_pad, _grad(sh.weight))
+    if not want_dseg:
+        return dx, None
     dsp = _sp_conv_bwd_data(da, sh.weight, _empty(n, ctx.seg_shape[1], h + 2, w + 2, dev))
     own = dsegs is None
     if own:
@@ -2482,8 +2485,9 @@ def spade_block_forward(blk, x, seg, keep=True, cache=None, weights_ready=False)
     return out, (ctx if keep else None)
 
 
-def spade_block_backward(blk, ctx, g, dsegs=None):
-    """g: gradient of the block's output.  Parameter gradients into .grad (overwritten); returns (dx, dseg) -- dseg as spade_norm_backward"""
+def spade_block_backward(blk, ctx, g, dsegs=None, want_dseg=True):
+    """g: gradient of the block's output.  Parameter gradients into .grad (overwritten); returns (dx, dseg) -- dseg and want_dseg as
+    spade_norm_backward"""
     g = g.contiguous()
     n, fin, h, w = ctx.x_shape
     dev = g.device
@@ -2493,20 +2497,20 @@ def spade_block_backward(blk, ctx, g, dsegs=None):
     w0, w1 = _sp_weight(blk.conv_0), _sp_weight(blk.conv_1)
     _sp_param_grads(blk.conv_1, g, ctx.p1)
     dp1 = _sp_conv_bwd_data(g, w1, _empty(n, w1.shape[1], h + 2, w + 2, dev))
-    dd0, _ = spade_norm_backward(blk.norm_1, ctx.n1, dp1, g_pad=1, dsegs=dsegs)
+    dd0, _ = spade_norm_backward(blk.norm_1, ctx.n1, dp1, g_pad=1, dsegs=dsegs, want_dseg=want_dseg)
     _sp_param_grads(blk.conv_0, dd0, ctx.p0)
     dp0 = _sp_conv_bwd_data(dd0, w0, _empty(n, fin, h + 2, w + 2, dev))
-    dx, _ = spade_norm_backward(blk.norm_0, ctx.n0, dp0, g_pad=1, dsegs=dsegs)
+    dx, _ = spade_norm_backward(blk.norm_0, ctx.n0, dp0, g_pad=1, dsegs=dsegs, want_dseg=want_dseg)
     if blk.learned_shortcut:
         ws = _sp_weight(blk.conv_s)
         _sp_param_grads(blk.conv_s, g, ctx.ps, k3=False)
         dps = ops.convk_bwd_data(g, ws, _empty(n, fin, h, w, dev), pad=0)
-        dxs, _ = spade_norm_backward(blk.norm_s, ctx.ns, dps, g_pad=0, dsegs=dsegs)
+        dxs, _ = spade_norm_backward(blk.norm_s, ctx.ns, dps, g_pad=0, dsegs=dsegs, want_dseg=want_dseg)
     else:
         dxs = g
     dx = ops.pad_affine(dx, (0, 0, 0, 0), 0, res=dxs)
     seg_shape = ctx.n0.seg_shape
-    return dx, (spade_dseg(dsegs, seg_shape, dev) if own else None)
+    return dx, (spade_dseg(dsegs, seg_shape, dev) if own and want_dseg else None)
 
 
 class SpadeCtx:
@@ -2549,12 +2553,15 @@ def spade_forward(G, seg, keep=True):
     return out, (ctx if keep else None)
 
 
-def spade_backward(G, ctx, dout):
-    """dout: gradient of the generator's (post-tanh) output.  Every parameter's .grad is overwritten; returns dseg."""
+def spade_backward(G, ctx, dout, want_dseg=True, pre_tanh=False):
+    """dout: gradient of the generator's (post-tanh) output.  Every parameter's .grad is overwritten; returns dseg.  want_dseg False: everything
+    that only serves the map's gradient is skipped (the input adjoints of every mlp_shared and of fc, the per-resolution accumulators, their
+    fold) and None is returned; the parameter gradients are the same launches on the same operands.  pre_tanh: dout is already the
+    gradient of the image head's PRE-tanh output (ops.g_out_grad folds the mask multiply and the tanh adjoint into one pass)."""
     dev = dout.device
     n = dout.shape[0]
     x = ctx.x_last
-    dz = ops.tanh_bwd(dout.contiguous(), ctx.out)
+    dz = dout.contiguous() if pre_tanh else ops.tanh_bwd(dout.contiguous(), ctx.out)
     ops.channel_sum(dz, _grad(G.conv_img.bias))
     _sp_wgrad(dz, ctx.p_last, _grad(G.conv_img.weight))
     dp = _sp_conv_bwd_data(dz, G.conv_img.weight, _empty(n, x.shape[1], x.shape[2] + 2, x.shape[3] + 2, dev))
@@ -2562,11 +2569,13 @@ def spade_backward(G, ctx, dout):
     g = ops.act_bwd(gc, x, LRELU, torch.empty_like(x))
     dsegs = {}
     for (blk, up), bctx in zip(reversed(_spade_plan(G)), reversed(ctx.blocks)):
-        g, _ = spade_block_backward(blk, bctx, g, dsegs=dsegs)
+        g, _ = spade_block_backward(blk, bctx, g, dsegs=dsegs, want_dseg=want_dseg)
         if up:
             g = ops.nearest_up2_bwd(g)
     ops.channel_sum(g, _grad(G.fc.bias))
     _sp_wgrad(g, ctx.s0_pad, _grad(G.fc.weight))
+    if not want_dseg:
+        return None
     ds0 = _sp_conv_bwd_data(g, G.fc.weight, _empty(n, ctx.seg_shape[1], G.sh + 2, G.sw + 2, dev))
     acc = dsegs.get((G.sh, G.sw))
     if acc is None:

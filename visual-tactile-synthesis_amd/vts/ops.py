@@ -1579,6 +1579,37 @@ def lpips_input_bwd(g, scale, dx, cx, accumulate=False, nstride=None):
     return dx
 
 
+def _chw_dense(t):
+    """the channels of every sample lie densely behind each other (a channel view of a contiguous NCHW tensor does; its batch stride is free)"""
+    _, c, h, w = t.shape
+    return t.stride(3) == 1 and t.stride(2) == w and (c == 1 or t.stride(1) == h * w)
+
+
+def vgg_stack_input(fake_I, fake_T, real_I, real_T):
+    """the VGG stem's zero-bordered operand [6 N, 3, H + 2, W + 2] of the three feature terms of a step as one batch: rows fake_I, fake_gx x 3,
+    fake_gy x 3, real_I, real_gx x 3, real_gy x 3 (gx, gy = tactile channels 0, 1).  Images [N, 3, H, W], tactile tensors [N, 2, H, W]; channel
+    views of wider tensors are fine (their batch stride is passed on)."""
+    n, _, h, w = fake_I.shape
+    assert fake_I.shape == real_I.shape == (n, 3, h, w) and fake_T.shape == real_T.shape == (n, 2, h, w)
+    assert all(t.dtype == torch.float32 and _chw_dense(t) for t in (fake_I, fake_T, real_I, real_T))
+    out = torch.empty(6 * n, 3, h + 2, w + 2, dtype=torch.float32, device=fake_I.device)
+    _run("vgg_stack_input", 4.0 * (out.numel() + 10 * n * h * w), 0.0, L.load().vts_vgg_stack_input, fake_I.data_ptr(), fake_I.stride(0), real_I.data_ptr(),
+         real_I.stride(0), fake_T.data_ptr(), fake_T.stride(0), real_T.data_ptr(), real_T.stride(0), n, h, w, out.data_ptr(), L.stream())
+    return out
+
+
+def vgg_stack_input_bwd(dx, d_fake_I, d_fake_T, accumulate=False):
+    """adjoint of vgg_stack_input on its 3 N fake rows: d_fake_I (+)= dx[:N]; d_fake_T[:, c] (+)= the sum of the three tiles of rows
+    [(1 + c) N, (2 + c) N), added as (0 + 1) + 2"""
+    n3, _, h, w = dx.shape
+    n = n3 // 3
+    assert dx.shape == (3 * n, 3, h, w) and dx.is_contiguous() and d_fake_I.shape == (n, 3, h, w) and d_fake_T.shape == (n, 2, h, w)
+    assert all(t.dtype == torch.float32 and _chw_dense(t) for t in (d_fake_I, d_fake_T))
+    _run("vgg_stack_input_bwd", 4.0 * (dx.numel() + 5 * n * h * w * (1 + bool(accumulate))), 0.0, L.load().vts_vgg_stack_input_bwd, dx.data_ptr(), n, h, w,
+         d_fake_I.data_ptr(), d_fake_I.stride(0), d_fake_T.data_ptr(), d_fake_T.stride(0), int(bool(accumulate)), L.stream())
+    return d_fake_I, d_fake_T
+
+
 # ---- SPADE generator (include/vts.h; reference models/normalization.py:68-112, models/architecture.py:21-68, models/networks.py:2075-2200) ----
 def spade_modulate(x, mean, rstd, gamma, beta, act=0, out_pad=0, out=None):
     """out = act(xhat (1 + gamma) + beta), xhat = (x - mean[n,c]) rstd[n,c]; out_pad 1: the zero-bordered [H+2][W+2] layout of the 3x3 GEMM-class

@@ -58,8 +58,9 @@ def _layout(net):
     return out
 
 
-def vgg_forward(net, x, keep_all=True, last_tap_only_needed=True):
-    """x [N, 3, H, W] (already in the network's input space).  Returns {conv index: (activation, zpad)}: every convolution when keep_all
+def vgg_forward(net, x, keep_all=True, last_tap_only_needed=True, padded_input=False):
+    """x [N, 3, H, W] (already in the network's input space); padded_input: x is already the stem's zero-bordered [N, 3, H + 2, W + 2]
+    operand (ops.vgg_stack_input writes it so) and the padding pass in front of convolution 0 is skipped.  Returns {conv index: (activation, zpad)}: every convolution when keep_all
     (a backward follows), else the tapped ones only.  Stops after the deepest tap.
       zpad 1  relu(z) in the interior of a zero-bordered [N, C, H + 2, W + 2] tensor -- written by the convolution itself
               (ops.conv3x3_wide_relu_pad) and read as it is by the next convolution: no pass in between
@@ -75,7 +76,7 @@ def vgg_forward(net, x, keep_all=True, last_tap_only_needed=True):
         conv = net.convs[k]
         co, ci = conv.weight.shape[:2]
         if k == 0:
-            p = ops.pad_affine(x, (1, 1, 1, 1), 0)      # (3 channels: the stem runs on the GEMM-class kernel too, one 8-channel chunk)
+            p = x if padded_input else ops.pad_affine(x, (1, 1, 1, 1), 0)      # (3 channels: the stem runs on the GEMM-class kernel too, one 8-channel chunk)
         else:
             pt, pz = prev
             if pooled:
@@ -269,3 +270,35 @@ def vgg_feature_l1(net, x, y, coeff, loss_slot, want_grad=True):
     if not want_grad:
         return None
     return vgg_backward(net, zx, tap_grads, tuple(x.shape))
+
+
+def vgg_feature_l1_stacked(net, fake_I, fake_T, real_I, real_T, coeff, slot_I, slot_T, d_fake_I=None, d_fake_T=None, accumulate=False):
+    """The three VGGLoss terms of a patch step (reference models/spade_model.py:662-675: the image; gx and gy each tiled to three channels)
+    as ONE batch of 6 N rows -- VGG has no batch statistics, so a row's features do not depend on its neighbours:
+        slot_I += coeff * VGGLoss(fake_I, real_I)
+        slot_T += coeff * (VGGLoss(fake_gx x 3, real_gx x 3) + VGGLoss(fake_gy x 3, real_gy x 3))
+    and d_fake_I [N, 3, H, W] / d_fake_T [N, 2, H, W] (+)= the gradients (created when not given; accumulate: added to what they hold).
+    One stacking launch writes the stem's padded operand (ops.vgg_stack_input), one forward runs over the 6 N rows, two L1 launches per tap
+    read contiguous row slices, one backward runs over the 3 N fake rows, one launch folds its result onto the five output channels.
+    The tactile rows [N, 3 N) are reduced with the element count of ONE N-row group, which makes the slot the SUM of the two means."""
+    n, _, h, w = fake_I.shape
+    p = ops.vgg_stack_input(fake_I, fake_T, real_I, real_T)
+    zz = vgg_forward(net, p, keep_all=True, padded_input=True)
+    del p
+    zx = {k: (t[:3 * n], zp) for k, (t, zp) in zz.items()}
+    tap_grads = {}
+    for wi, k in zip(net.weights, net.taps):
+        t, zp = zz[k]
+        count = n * t.shape[1] * (t.shape[2] - 2 * zp) * (t.shape[3] - 2 * zp)
+        g = torch.empty_like(zx[k][0])
+        ops.l1_relu(t[:n], t[3 * n:4 * n], coeff * wi / count, slot_I, grad=g[:n])
+        ops.l1_relu(t[n:3 * n], t[4 * n:], coeff * wi / count, slot_T, grad=g[n:])
+        tap_grads[k] = g
+    del zz
+    dx = vgg_backward(net, zx, tap_grads, (3 * n, 3, h, w))
+    if (d_fake_I is None) != (d_fake_T is None) or (accumulate and d_fake_I is None):
+        raise ValueError("vgg_feature_l1_stacked: give both gradient destinations or neither; accumulate needs them")
+    if d_fake_I is None:
+        d_fake_I = torch.empty(n, 3, h, w, dtype=torch.float32, device=dx.device)
+        d_fake_T = torch.empty(n, 2, h, w, dtype=torch.float32, device=dx.device)
+    return ops.vgg_stack_input_bwd(dx, d_fake_I, d_fake_T, accumulate=accumulate)

@@ -8,6 +8,17 @@
 // bias / tanh / derivative mask / accumulate epilogue, exact fp32 MFMA (v_mfma_f32_16x16x4_f32).
 // LDS holds the zero-haloed (halo = 2) input planes of IPB images x CK channels; per-lane A-fragment
 // bases are looked up per unit, everything else is uniform.
+//
+// Two staging paths, one instance each (template parameter NQ), the same values at the same LDS places and the same MFMA sequence:
+//   NQ = 3 / 6 / 10  pipelined flat staging: every single-source launch with Cin % 8 == 0 and contiguous samples -- all hidden layers
+//                    of the D2 patch stacks, forward and transposed, with or without dmask / accumulate, maps 2 x 2 .. 20 x 20.  NQ is
+//                    the number of 16-byte quads a thread holds per chunk; the host picks the smallest that covers IPB images.
+//                    The quad loads need dword alignment only: weight views of the optimiser's flat parameter buffer (4-byte aligned
+//                    behind the first one-float head bias) and [1:] views take this path.
+//   NQ = 0           line-wise staging: dual source, Cin % 8 != 0 (the 7-channel 16 x 16 / 8 x 8 first layers, the 1-channel head adjoints),
+//                    strided samples.  One barrier pair per chunk and no prefetch of chunk k + 1 (its line count is not bounded by a
+//                    register array).
+// Both read scale and shift from an LDS table [IPB][Cin] filled once per workgroup (no per-element global loads of them).
 #include <stdlib.h>
 
 #include "vts_internal.h"
@@ -37,11 +48,11 @@ struct SmallK {
   int GH, GW, PPI, MTP; // phase-grid dims, pixels per image per phase, M-tiles per phase
   int ablate;           // profiling only (env VTS_ABLATE)
   int wbytes;           // extent of the weight view in bytes (buffer descriptor)
-  int fast;             // 1: pipelined flat staging (single source, Cin % 8 == 0, contiguous samples: see the kernel)
+  int fast;             // > 0: pipelined flat staging with that many quads per thread (single source, Cin % 8 == 0, contiguous samples: see the kernel)
   int inbytes;          // extent of the input tensor in bytes (buffer descriptor of the flat loads)
 };
 
-template <int MODE, int S, int NR, int UMAX, int CK>
+template <int MODE, int S, int NR, int UMAX, int CK, int NQ>
 __global__ __launch_bounds__(256) void conv_small_kernel(const SmallK p) {
   constexpr int P = (MODE == 1 && S == 2) ? 4 : 1;
   constexpr int COP = (NR % 2 == 1) ? NR * 16 : NR * 16 + 16;
@@ -60,6 +71,24 @@ __global__ __launch_bounds__(256) void conv_small_kernel(const SmallK p) {
   const int npix = p.IPB * p.PPI;
   const int nunits = p.MTP * P;
 
+  // per-(image, channel) scale and shift of the concatenated input, read once per workgroup into an LDS table (absent images: the
+  // last one's, unused); the first two entries per thread are in flight under the zeroing and the decode tables
+  float* aff_sc = reinterpret_cast<float*>(line_tab + p.IPB * CK * p.IH);   // [IPB][Cin] scale, then shift
+  float* aff_sh = aff_sc + p.IPB * p.Cin;
+  const int naff = p.IPB * p.Cin;
+  auto affine_of = [&](int i, float& sc, float& sh) {
+    const int img = i / p.Cin, ci = i - img * p.Cin;
+    const int nn = min(n0 + img, p.N - 1);
+    const bool first = ci < p.C0;
+    const float* scp = first ? p.sc0 : p.sc1;
+    const float* shp = first ? p.sh0 : p.sh1;
+    const int aidx = first ? nn * p.C0 + ci : nn * p.C1 + ci - p.C0;
+    sc = scp ? scp[aidx] : 1.f;
+    sh = shp ? shp[aidx] : 0.f;
+  };
+  float asc[2], ash[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) affine_of(min(tid + 256 * j, naff - 1), asc[j], ash[j]);
   // zero the whole patch once: halos (and rows of absent images / channels) stay zero
   for (int i = tid; i < p.IPB * CK * p.plane; i += 256) patch[i] = 0.f;
   // decode tables (integer divisions by run-time sizes happen once per entry, not per use)
@@ -73,6 +102,10 @@ __global__ __launch_bounds__(256) void conv_small_kernel(const SmallK p) {
     const int c = rem / p.IH, y = rem - c * p.IH;
     line_tab[l] = (img << 16) | (c << 8) | y;
   }
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+    if (tid + 256 * j < naff) { aff_sc[tid + 256 * j] = asc[j]; aff_sh[tid + 256 * j] = ash[j]; }
+  for (int i = tid + 512; i < naff; i += 256) affine_of(i, aff_sc[i], aff_sh[i]);
   __syncthreads();
 
   // per-lane A-fragment base of every unit this wave owns (unit = one 16-pixel M-tile of one phase)
@@ -146,24 +179,19 @@ __global__ __launch_bounds__(256) void conv_small_kernel(const SmallK p) {
     }
   };
 
-  if (p.fast) {
+  if constexpr (NQ > 0) {
     // ---- pipelined flat staging (round 3).  The line-wise staging below spends one wave instruction per 2 map rows -- 5 - 9 useful lanes
     // of 32 on these maps -- and waits for every chunk's loads before it multiplies: 33 of 65 us on the 32 -> 64 layer of 640 5 x 5 maps
     // (tools/mb_small.py, VTS_ABLATE).  A chunk of 8 channels of one sample is 8 * IH * IW CONTIGUOUS floats: threads load 16-byte
     // quads of that run (fully used lanes), the quad -> (channel, y, x) decode is done once (it is the same for every chunk), and the
     // quads and the weight slice of chunk k + 1 are in flight during the MFMA phase of chunk k.
-    constexpr int NQ = 3;                                   // quads per thread (the host side checks IPB * 2 * IH * IW <= 768)
+    // NQ quads per thread: the host side picks the smallest instance with IPB * 2 * IH * IW <= 256 * NQ (3: maps up to 9 x 9 and
+    // the blocks of the 2 x 2 .. 6 x 6 maps, 6: two images of 17 x 17, 10: whatever else the LDS cap admits).  The 16-byte buffer loads
+    // need dword alignment only (tools/probes/x4_unaligned_bw.hip: same rate), so neither the input nor the weight view has to be
+    // 16-byte aligned -- the weights of the optimiser's flat parameter buffer are not, behind the first one-float head bias.
     constexpr int NCO = NR * 16;
     constexpr int NWQ = CK * 4 * NCO / 256;                 // weight quads per thread
-    float* aff_sc = reinterpret_cast<float*>(line_tab + p.IPB * CK * p.IH);   // [IPB][Cin] scale, then shift
-    float* aff_sh = aff_sc + p.IPB * p.Cin;
     const int HW = p.IH * p.IW, QPI = 2 * HW, nq = p.IPB * QPI;
-    for (int i = tid; i < p.IPB * p.Cin; i += 256) {
-      const int img = i / p.Cin, ci = i - img * p.Cin;
-      const int nn = min(n0 + img, p.N - 1);
-      aff_sc[i] = p.sc0 ? p.sc0[nn * p.C0 + ci] : 1.f;
-      aff_sh[i] = p.sh0 ? p.sh0[nn * p.C0 + ci] : 0.f;
-    }
     unsigned qoff[NQ];
     int qpk[NQ][4];                                         // (affine index << 16) | patch offset of the four elements
 #pragma unroll
@@ -231,7 +259,6 @@ __global__ __launch_bounds__(256) void conv_small_kernel(const SmallK p) {
 #pragma unroll
     for (int e = 0; e < NWQ; ++e) wq[e] = (f32x4){0.f, 0.f, 0.f, 0.f};
     load_chunk(0);
-    __syncthreads();          // affine table complete
     store_chunk(0);
     __syncthreads();
     for (int chunk = 0; chunk < nchunks; ++chunk) {
@@ -244,7 +271,7 @@ __global__ __launch_bounds__(256) void conv_small_kernel(const SmallK p) {
       }
     }
   } else
-  for (int chunk = 0; chunk < nchunks; ++chunk) {
+  for (int chunk = 0; chunk < nchunks; ++chunk) {   // NQ == 0: line-wise staging (dual source, Cin % 8 != 0, strided samples)
     const int cbase = chunk * CK;
     // ---- stage input lines: unconditional clamped loads first, branch-free finish afterwards ----
     if (!(p.ablate & 1))
@@ -260,12 +287,8 @@ __global__ __launch_bounds__(256) void conv_small_kernel(const SmallK p) {
         const int cl = first ? cic : cic - p.C0;
         const float* base = first ? p.s0 + nn * p.ns0 : p.s1 + nn * p.ns1;
         raw[b] = base[cl * iplane + (int64_t)y * p.IW + min(xl, p.IW - 1)];
-        const float* scp = first ? p.sc0 : p.sc1;
-        const float* shp = first ? p.sh0 : p.sh1;
-        const int aidx = nn * (first ? p.C0 : p.C1) + cl;
-        const bool hsc = scp != nullptr, hsh = shp != nullptr;
-        rsc[b] = (hsc ? scp : p.ident)[hsc ? aidx : 0];
-        rsh[b] = (hsh ? shp : p.ident)[hsh ? aidx : 1];
+        rsc[b] = aff_sc[img * p.Cin + cic];
+        rsh[b] = aff_sh[img * p.Cin + cic];
       }
 #pragma unroll
       for (int b = 0; b < 8; ++b) {
@@ -357,13 +380,23 @@ __global__ __launch_bounds__(256) void conv_small_kernel(const SmallK p) {
   }
 }
 
-template <int MODE, int S, int NR, int UMAX, int CK>
-int launch_small(const SmallK& k, size_t lds_bytes, hipStream_t st) {
+template <int MODE, int S, int NR, int UMAX, int CK, int NQ>
+int launch_small_nq(const SmallK& k, size_t lds_bytes, hipStream_t st) {
   dim3 grid(cdiv(k.N, k.IPB), cdiv(k.Cout, NR * 16));
-  hipLaunchKernelGGL((conv_small_kernel<MODE, S, NR, UMAX, CK>), grid, dim3(256), lds_bytes, st, k);
-  vts_set_kernel("conv_small_kernel<%d, %d, %d, %d, %d>%s", MODE, S, NR, UMAX, CK, k.fast ? "+flat" : "");
+  hipLaunchKernelGGL((conv_small_kernel<MODE, S, NR, UMAX, CK, NQ>), grid, dim3(256), lds_bytes, st, k);
+  vts_set_kernel("conv_small_kernel<%d, %d, %d, %d, %d>%s", MODE, S, NR, UMAX, CK, NQ ? "+flat" : "");
   VTS_CHECK_LAUNCH("vts_conv4x4 (small maps)");
   return VTS_OK;
+}
+
+template <int MODE, int S, int NR, int UMAX, int CK>
+int launch_small(const SmallK& k, size_t lds_bytes, hipStream_t st) {
+  switch (k.fast) {   // quads per thread of the flat staging (0: line-wise)
+    case 0: return launch_small_nq<MODE, S, NR, UMAX, CK, 0>(k, lds_bytes, st);
+    case 3: return launch_small_nq<MODE, S, NR, UMAX, CK, 3>(k, lds_bytes, st);
+    case 6: return launch_small_nq<MODE, S, NR, UMAX, CK, 6>(k, lds_bytes, st);
+    default: return launch_small_nq<MODE, S, NR, UMAX, CK, 10>(k, lds_bytes, st);
+  }
 }
 
 }  // namespace
@@ -423,9 +456,13 @@ int vts_conv_small_try(const vts_conv_desc* d, hipStream_t st) {
   if (upw > 8) return VTS_ERR_UNSUPPORTED;
   const int U = upw <= 1 ? 1 : (upw <= 2 ? 2 : (upw <= 4 ? 4 : 8));
   k.inbytes = (int)((int64_t)d->N * d->in0.nstride * 4 < (int64_t)0x40000000 ? (int64_t)d->N * d->in0.nstride * 4 : 0);
-  k.fast = !d->in1.data && k.Cin % CK == 0 && d->in0.nstride == (int64_t)k.Cin * d->IH * d->IW && (reinterpret_cast<uintptr_t>(d->in0.data) & 15) == 0 &&
-           ipb * 2 * d->IH * d->IW <= 768 && k.inbytes > 0 && (reinterpret_cast<uintptr_t>(d->w) & 15) == 0 && ((d->ws_co | d->ws_ci) & 3) == 0;
-  const size_t lds = (size_t)(ipb * CK * k.plane + CK * 16 * COP + k.MTP * 16 + ipb * CK * d->IH + (k.fast ? 2 * ipb * k.Cin : 0)) * sizeof(float);
+  // flat staging: single source, whole 8-channel chunks, contiguous samples (dword alignment is enough for its 16-byte loads); the
+  // packed decode holds the patch offset in 16 bits and the affine index in 15
+  const int nqt = cdiv(ipb * 2 * d->IH * d->IW, 256);
+  const bool flat = !d->in1.data && k.Cin % CK == 0 && d->in0.nstride == (int64_t)k.Cin * d->IH * d->IW && nqt <= 10 && k.inbytes > 0 &&
+                    ((d->ws_co | d->ws_ci) & 3) == 0 && ipb * CK * k.plane <= 0x10000 && ipb * k.Cin < 0x8000;
+  k.fast = !flat ? 0 : (nqt <= 3 ? 3 : (nqt <= 6 ? 6 : 10));
+  const size_t lds = (size_t)(ipb * CK * k.plane + CK * 16 * COP + k.MTP * 16 + ipb * CK * d->IH + 2 * ipb * k.Cin) * sizeof(float);
 #define SMALL_U(MODE, S, NRV)                                                  \
   switch (U) {                                                                 \
     case 1: return launch_small<MODE, S, NRV, 1, CK>(k, lds, st);              \

@@ -540,6 +540,11 @@ __global__ __launch_bounds__(256) void wgrad4x4_ns_kernel(const WgK p) {
 // the plane offset of every position's window, and the four waves split the high-res channels while each holds all low-res
 // channel tiles: per group of four positions CLT + CHW LDS reads feed CLT x CHW MFMAs.  A workgroup keeps the whole CL x CH x 16
 // result in registers across its image blocks and writes ONE partial copy (reduced by wgrad_reduce_batch_kernel as for the others).
+// Staging (template parameter QUADS): where the samples of both operands are contiguous -- every launch of the D2 patch stacks -- the
+// images of a block are one run of each operand, loaded as 16-byte quads (dword alignment is enough) in rounds of SW_RQ per thread,
+// the next round issued before the current one is finished into LDS, scale and shift from an LDS table filled once per block
+// ("+quad" in vts_last_kernel); otherwise element by element as in round 2.  Same values at the same LDS places: IPB, nblocks, the
+// number of partial copies and the position order, and with them every bit of the result, do not depend on the staging.
 struct SmallWK {
   const float *lo, *losc, *losh, *hi, *hisc, *hish;
   int64_t lons, hins;
@@ -547,8 +552,11 @@ struct SmallWK {
   float lo_slope, hi_slope;
   int IPB, nblocks, POS, POSP, PW_, PLANE;   // positions per block (multiple of 4), lo row pitch, hi row pitch / plane (floats)
   float* part;
+  int quads;              // 1: both operands have contiguous samples: quad staging (the QUADS instances); 0: element-wise staging
+  int lobytes, hibytes;   // extents of the operands in bytes (buffer descriptors of the quad loads)
 };
 constexpr int SW_HALO = 2;
+constexpr int SW_RQ = 8;   // quad staging: 16-byte loads per thread and round
 
 // e / d for 0 <= e < 2^23 through the float reciprocal (off by at most one: fixed up); ~8 instructions instead of the ~40 of a 32-bit division
 __device__ __forceinline__ int fdiv(int e, int d, float inv, int& rem) {
@@ -560,7 +568,7 @@ __device__ __forceinline__ int fdiv(int e, int d, float inv, int& rem) {
   return q;
 }
 
-template <int CLT, int CHW>
+template <int CLT, int CHW, bool QUADS>
 __global__ __launch_bounds__(256) void wgrad_small_kernel(const SmallWK p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* lo_t = smem;                                   // [CLT*16][POSP]
@@ -573,6 +581,87 @@ __global__ __launch_bounds__(256) void wgrad_small_kernel(const SmallWK p) {
   const int imgstride = p.CH * p.PLANE;
   const float inv_blk = 1.f / (float)(p.IPB * lhw), inv_lhw = 1.f / (float)lhw, inv_hhw = 1.f / (float)hhw, inv_ch = 1.f / (float)p.CH,
               inv_hw = 1.f / (float)p.HW;
+  const int tapoff = (m16 >> 2) * p.PW_ + (m16 & 3);     // B fragment: column n = tap (ky, kx)
+  f32x4 acc[CLT][CHW];
+#pragma unroll
+  for (int t = 0; t < CLT; ++t)
+#pragma unroll
+    for (int c = 0; c < CHW; ++c) acc[t][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  // ---- quad staging (round 10).  The IPB samples of a block are ONE contiguous run of each operand, so a thread loads 16-byte quads
+  // of the run (dword alignment is enough for buffer loads) with no decode in front of the load: a round is SW_RQ quads per thread,
+  // all in flight at once, and the next round -- lo rounds first, then the hi rounds -- is issued before the current one is finished
+  // into LDS.  The element -> (LDS offset, affine index) decode runs once per quad under those loads (one reciprocal division chain,
+  // then carries); scale and shift come from an LDS table filled once per block.  The first round of a workgroup's next block is in
+  // flight during the MFMA phase.  Same values at the same LDS places as the element-wise staging below: the sums keep their order.
+  float* aff = reinterpret_cast<float*>(postab + p.POS);   // [IPB * CL] lo scale, lo shift, [IPB * CH] hi scale, hi shift
+  const int naff_lo = p.IPB * p.CL, naff_hi = p.IPB * p.CH;
+  f32x4 qa[SW_RQ], qb[SW_RQ];
+  // round r of block blk: the lo rounds [0, rl) cover the run of nimg * CL * lhw floats, the hi rounds the run of nimg * CH * hhw
+  auto issue = [&](f32x4 (&v)[SW_RQ], int blk, int r, int rl) {
+    const int nimg = min(p.IPB, p.N - blk * p.IPB);
+    const bool is_lo = r < rl;
+    const int run = is_lo ? nimg * p.CL * lhw : nimg * p.CH * hhw;
+    const int q0 = (is_lo ? r : r - rl) * (256 * SW_RQ) + tid;
+    const int base = (int)((int64_t)blk * p.IPB * (is_lo ? p.lons : p.hins) * 4);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(is_lo ? p.lo : p.hi), 0, is_lo ? p.lobytes : p.hibytes, 0x00020000);
+#pragma unroll
+    for (int j = 0; j < SW_RQ; ++j) {
+      const int q = q0 + 256 * j;
+      // the whole address is the checked offset: the dwords of a last quad that lie behind the tensor read as zero, quads behind the run are not loaded
+      const int vo = 4 * q < run ? base + 16 * q : 0x40000000;
+      v[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, 0, 0));
+    }
+  };
+  auto finish = [&](const f32x4 (&v)[SW_RQ], int blk, int r, int rl) {
+    const int nimg = min(p.IPB, p.N - blk * p.IPB);
+    if (r < rl) {
+      const int run = nimg * p.CL * lhw, clhw = p.CL * lhw;
+      const float inv_clhw = 1.f / (float)clhw;
+#pragma unroll
+      for (int j = 0; j < SW_RQ; ++j) {
+        const int e = 4 * (r * (256 * SW_RQ) + tid + 256 * j);
+        if (e >= run) continue;
+        int rem, x;
+        int img = fdiv(e, clhw, inv_clhw, rem);
+        int c = fdiv(rem, lhw, inv_lhw, x);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (e + k < run) {
+            const int ai = img * p.CL + c;
+            const float t = fmaf(v[j][k], aff[ai], aff[naff_lo + ai]);
+            lo_t[c * p.POSP + img * lhw + x] = fmaxf(t, 0.f) + p.lo_slope * fminf(t, 0.f);
+          }
+          if (++x == lhw) { x = 0; if (++c == p.CL) { c = 0; ++img; } }
+        }
+      }
+    } else {
+      const int run = nimg * p.CH * hhw, chhw = p.CH * hhw;
+      const float inv_chhw = 1.f / (float)chhw;
+      const float* hsc = aff + 2 * naff_lo;
+#pragma unroll
+      for (int j = 0; j < SW_RQ; ++j) {
+        const int e = 4 * ((r - rl) * (256 * SW_RQ) + tid + 256 * j);
+        if (e >= run) continue;
+        int rem, pos, x;
+        int img = fdiv(e, chhw, inv_chhw, rem);
+        int c = fdiv(rem, hhw, inv_hhw, pos);
+        int y = fdiv(pos, p.HW, inv_hw, x);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (e + k < run) {
+            const int ai = img * p.CH + c;
+            const float t = fmaf(v[j][k], hsc[ai], hsc[naff_hi + ai]);
+            hi_t[img * imgstride + c * p.PLANE + (y + SW_HALO) * p.PW_ + x + SW_HALO] = fmaxf(t, 0.f) + p.hi_slope * fminf(t, 0.f);
+          }
+          if (++x == p.HW) { x = 0; if (++y == p.HH) { y = 0; if (++c == p.CH) { c = 0; ++img; } } }
+        }
+      }
+    }
+  };
+  auto rounds_lo = [&](int blk) { return (min(p.IPB, p.N - blk * p.IPB) * p.CL * lhw + 1024 * SW_RQ - 1) / (1024 * SW_RQ); };
+  auto rounds_hi = [&](int blk) { return (min(p.IPB, p.N - blk * p.IPB) * p.CH * hhw + 1024 * SW_RQ - 1) / (1024 * SW_RQ); };
+  if (QUADS && (int)blockIdx.x < p.nblocks) issue(qa, blockIdx.x, 0, rounds_lo(blockIdx.x));   // in flight under the zeroing
   // zero everything once: halos, padded positions and absent channel rows stay zero
   for (int i = tid; i < CLT * 16 * p.POSP + p.IPB * imgstride; i += 256) smem[i] = 0.f;
   for (int q = tid; q < p.POS; q += 256) {
@@ -580,17 +669,44 @@ __global__ __launch_bounds__(256) void wgrad_small_kernel(const SmallWK p) {
     const int y = rem / p.LW, x = rem - y * p.LW;
     postab[q] = img < p.IPB ? img * imgstride + (y * p.S - p.pad + SW_HALO) * p.PW_ + (x * p.S - p.padx + SW_HALO) : 0;
   }
-  const int tapoff = (m16 >> 2) * p.PW_ + (m16 & 3);     // B fragment: column n = tap (ky, kx)
-  f32x4 acc[CLT][CHW];
-#pragma unroll
-  for (int t = 0; t < CLT; ++t)
-#pragma unroll
-    for (int c = 0; c < CHW; ++c) acc[t][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
   __syncthreads();
 
   for (int blk = blockIdx.x; blk < p.nblocks; blk += gridDim.x) {
     const int n0 = blk * p.IPB;
     const int nimg = min(p.IPB, p.N - n0);
+    if constexpr (QUADS) {
+      for (int i = tid; i < naff_lo; i += 256) {
+        const int img = i / p.CL, c = i - img * p.CL;
+        const int n = n0 + min(img, nimg - 1);
+        aff[i] = p.losc ? p.losc[n * p.CL + c] : 1.f;
+        aff[naff_lo + i] = p.losh ? p.losh[n * p.CL + c] : 0.f;
+      }
+      for (int i = tid; i < naff_hi; i += 256) {
+        const int img = i / p.CH, c = i - img * p.CH;
+        const int n = n0 + min(img, nimg - 1);
+        aff[2 * naff_lo + i] = p.hisc ? p.hisc[n * p.CH + c] : 1.f;
+        aff[2 * naff_lo + naff_hi + i] = p.hish ? p.hish[n * p.CH + c] : 0.f;
+      }
+      // a ragged block behind a full one: the positions of the last, partly filled group that belong to no image are zero
+      if (nimg < p.IPB)
+        for (int i = tid; i < CLT * 16 * 4; i += 256) {
+          const int pos = nimg * lhw + (i & 3);
+          if (pos < p.POS) lo_t[(i >> 2) * p.POSP + pos] = 0.f;
+        }
+      __syncthreads();      // affine table complete (first block: LDS zeroed)
+      const int rl = rounds_lo(blk), nr = rl + rounds_hi(blk);
+      for (int r = 0; r < nr; r += 2) {       // round r is in flight in qa
+        if (r + 1 < nr) issue(qb, blk, r + 1, rl);
+        finish(qa, blk, r, rl);
+        if (r + 1 < nr) {
+          if (r + 2 < nr) issue(qa, blk, r + 2, rl);
+          finish(qb, blk, r + 1, rl);
+        }
+      }
+      __syncthreads();
+      const int nb = blk + gridDim.x;
+      if (nb < p.nblocks) issue(qa, nb, 0, rounds_lo(nb));   // the next block's first round, under this block's MFMAs
+    } else {
     // ---- stage lo [cl][pos] (positions of absent images: zero) and the interior of the hi planes
     // (batches of 8 elements per thread: the global loads of a batch are all in flight before the first LDS store)
     const int lo_total = p.CL * p.IPB * lhw;
@@ -641,6 +757,7 @@ __global__ __launch_bounds__(256) void wgrad_small_kernel(const SmallWK p) {
       }
     }
     __syncthreads();
+    }
     // ---- MFMA over groups of four positions, UG groups per iteration: all LDS reads of an iteration are issued before its MFMAs (one
     // wave per SIMD at this LDS footprint: nothing else hides the read latency)
     const int ngroups = (nimg * lhw + 3) >> 2;
@@ -973,7 +1090,7 @@ Plan make_plan(const vts_wgrad_desc* d) {
         static const int lds_cap_kb = vts_tune("VTS_WGRAD_SMALL_LDS_KB", 150);
         if (floats * 4 <= (int64_t)lds_cap_kb * 1024 || (ipb == 1 && floats * 4 <= 150 * 1024)) {
           pl.small = 1; pl.clt = clt; pl.cht = chw; pl.ipb = ipb; pl.pos = pos; pl.posp = posp; pl.pwf = pwf; pl.plane = plane;
-          pl.lds_bytes = (int)(floats * 4);
+          pl.lds_bytes = (int)((floats + 2 * ipb * (CL + CH)) * 4);   // + the affine table of the quad staging (not part of the choice of ipb)
           pl.nblocks = cdiv(d->N, ipb);
           pl.pw = pl.nblocks < 256 ? pl.nblocks : 256;
           pl.cl_groups = pl.ch_groups = 1; pl.tiles_y = pl.tiles_x = pl.ntiles = 0; pl.txl = 0;
@@ -1197,16 +1314,22 @@ extern "C" int vts_wgrad4x4(const vts_wgrad_desc* d, float* ws, void* stream) {
     q.lo_slope = vts_slope(d->act_lo); q.hi_slope = vts_slope(d->act_hi);
     q.IPB = pl.ipb; q.nblocks = pl.nblocks; q.POS = pl.pos; q.POSP = pl.posp; q.PW_ = pl.pwf; q.PLANE = pl.plane;
     q.part = ws;
+    // quad staging: the samples of each operand back to back (a block of images is one contiguous run), offsets within the buffer descriptor
+    const int64_t lob = (int64_t)d->N * d->lo0.nstride * 4, hib = (int64_t)d->N * d->hi0.nstride * 4;
+    q.quads = d->lo0.nstride == (int64_t)q.CL * d->LH * d->LW && d->hi0.nstride == (int64_t)q.CH * d->HH * d->HW && lob < 0x40000000 && hib < 0x40000000;
+    q.lobytes = q.quads ? (int)lob : 0; q.hibytes = q.quads ? (int)hib : 0;
     bool ok = false;
 #define SW_CASE(CLT, CHW)                                                                                                      \
   if (pl.clt == CLT && pl.cht == CHW) {                                                                                        \
-    static bool attr = false;                                                                                                  \
-    if (!attr) {                                                                                                               \
-      (void)hipFuncSetAttribute((const void*)wgrad_small_kernel<CLT, CHW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-      attr = true;                                                                                                             \
+    const void* fn = q.quads ? (const void*)wgrad_small_kernel<CLT, CHW, true> : (const void*)wgrad_small_kernel<CLT, CHW, false>; \
+    static bool attr[2] = {false, false};                                                                                      \
+    if (!attr[q.quads]) {                                                                                                      \
+      (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                                   \
+      attr[q.quads] = true;                                                                                                    \
     }                                                                                                                          \
-    hipLaunchKernelGGL((wgrad_small_kernel<CLT, CHW>), dim3(pl.pw), dim3(256), pl.lds_bytes, st, q);                           \
-    vts_set_kernel("wgrad_small_kernel<%d, %d>", CLT, CHW);                                                                    \
+    if (q.quads) hipLaunchKernelGGL((wgrad_small_kernel<CLT, CHW, true>), dim3(pl.pw), dim3(256), pl.lds_bytes, st, q);        \
+    else hipLaunchKernelGGL((wgrad_small_kernel<CLT, CHW, false>), dim3(pl.pw), dim3(256), pl.lds_bytes, st, q);               \
+    vts_set_kernel("wgrad_small_kernel<%d, %d>%s", CLT, CHW, q.quads ? "+quad" : "");                                          \
     ok = true;                                                                                                                 \
   }
     SW_CASE(1, 2) SW_CASE(1, 4) SW_CASE(1, 8) SW_CASE(1, 16) SW_CASE(2, 2) SW_CASE(2, 4) SW_CASE(2, 8) SW_CASE(2, 16) SW_CASE(4, 2) SW_CASE(4, 4)

@@ -306,6 +306,140 @@ def norm_bwd(dy, x, mean, rstd, mode, *, gamma=None, dgamma0=None, dbeta0=None, 
     return out
 
 
+# ---- the GEMM-class "wide" ABI (vts_conv3x3_wide / _s2 / vts_tconv3x3s2_wide / vts_conv4x4_wide / vts_wgrad3x3_wide / vts_wgrad4x4_wide) ------
+# Written from the formulas of include/vts.h.  Inputs are the PRE-PADDED identity operands the entries take; weights are the operator's
+# UNPACKED weight (what vts_w3x3_pack / vts_w4x4_pack read), not the packed buffer.
+
+def _valid_conv(p, w, K, s, oh, ow):
+    """sum_{ci, ky, kx} p[n, ci, s y + ky, s x + kx] w[co, ci, ky, kx], one matmul per tap"""
+    n, cin = p.shape[:2]
+    cout = w.shape[0]
+    out = p.new_zeros(n, cout, oh, ow)
+    for ky in range(K):
+        for kx in range(K):
+            sl = p[:, :, ky:ky + (oh - 1) * s + 1:s, kx:kx + (ow - 1) * s + 1:s].reshape(n, cin, oh * ow)
+            out += torch.matmul(w[:, :, ky, kx], sl).view(n, cout, oh, ow)
+    return out
+
+
+def _pad1(t):
+    return torch.nn.functional.pad(t, (1, 1, 1, 1))
+
+
+def conv_wide(p, w, bias, *, K, stride, out_hw=None, epilogue=None, mask=None, add=None):
+    """vts_conv3x3_wide / vts_conv3x3s2_wide / vts_conv4x4_wide (transposed = 0): the valid K x K convolution (K 3 | 4) of the pre-padded
+    p [N, Cin, PH, PW] with the operator weight w [Cout, Cin, K, K], stride 1 | 2; K_terms = Cin K^2.  out_hw: the output extent where the
+    entry is told it (4 x 4), else the largest that fits.
+    epilogue "relu_pad" (vts_conv3x3_wide_relu_pad): max(ref, 0) inside a one-pixel border of exact zeros, the unit unchanged;
+    "mask_pad" (vts_conv3x3_wide_mask_pad): (ref + add) where mask > 0, else exactly 0; mask / add in the padded layout [N, Cout, H + 2, W + 2]."""
+    p, w = _f64(p), _f64(w)
+    assert w.shape[1] == p.shape[1] and w.shape[2:] == (K, K) and stride in (1, 2)
+    oh, ow = out_hw if out_hw is not None else ((p.shape[2] - K) // stride + 1, (p.shape[3] - K) // stride + 1)
+    assert p.shape[2] >= stride * (oh - 1) + K and p.shape[3] >= stride * (ow - 1) + K
+    ref = _valid_conv(p, w, K, stride, oh, ow)
+    absref = _valid_conv(p.abs(), w.abs(), K, stride, oh, ow)
+    if bias is not None:
+        b = _f64(bias).view(1, -1, 1, 1)
+        ref, absref = ref + b, absref + b.abs()
+    scale = U * math.sqrt(w.shape[1] * K * K)
+    if epilogue is None:
+        return {"out": (ref, scale * absref)}
+    if epilogue == "relu_pad":
+        return {"out": (_pad1(ref.clamp_min(0)), _pad1(scale * absref))}
+    assert epilogue == "mask_pad" and mask is not None
+    ref, absref = _pad1(ref), _pad1(absref)
+    if add is not None:
+        ref, absref = ref + _f64(add), absref + _f64(add).abs()
+    keep = (_f64(mask) > 0).to(torch.float64)
+    keep[:, :, 0], keep[:, :, -1], keep[:, :, :, 0], keep[:, :, :, -1] = 0, 0, 0, 0       # the border is zero whatever the mask holds
+    return {"out": (ref * keep, scale * absref * keep)}
+
+
+def _tconv_s2(p, w, K, pad, oh, ow):
+    """out[n, b, 2 i + ky - pad, 2 j + kx - pad] += p[n, a, i, j] w[a, b, ky, kx] (scatter form), and the number of taps that reach
+    each output element: (sum [N, B, OH, OW], taps [OH, OW])"""
+    n, cin, ih, iw = p.shape
+    cout = w.shape[1]
+    out = p.new_zeros(n, cout, oh, ow)
+    taps = p.new_zeros(oh, ow)
+    for ky in range(K):
+        ii = [i for i in range(ih) if 0 <= 2 * i + ky - pad < oh]
+        for kx in range(K):
+            jj = [j for j in range(iw) if 0 <= 2 * j + kx - pad < ow]
+            if not ii or not jj:
+                continue
+            sl = p[:, :, ii[0]:ii[-1] + 1, jj[0]:jj[-1] + 1].reshape(n, cin, len(ii) * len(jj))
+            y0, x0 = 2 * ii[0] + ky - pad, 2 * jj[0] + kx - pad
+            out[:, :, y0:y0 + 2 * len(ii):2, x0:x0 + 2 * len(jj):2] += torch.matmul(w[:, :, ky, kx].T, sl).view(n, cout, len(ii), len(jj))
+            taps[y0 % 2::2, x0 % 2::2] += 1      # every element of that parity phase sums this tap (rows beyond the data are the appended zeros)
+    return out, taps
+
+
+def _tconv_judge(p, w, bias, K, pad, oh, ow):
+    p, w = _f64(p), _f64(w)
+    assert w.shape[0] == p.shape[1] and w.shape[2:] == (K, K)
+    ref, taps = _tconv_s2(p, w, K, pad, oh, ow)
+    absref, _ = _tconv_s2(p.abs(), w.abs(), K, pad, oh, ow)
+    if bias is not None:
+        b = _f64(bias).view(1, -1, 1, 1)
+        ref, absref = ref + b, absref + b.abs()
+    return {"out": (ref, U * torch.sqrt(p.shape[1] * taps).view(1, 1, oh, ow) * absref)}
+
+
+def tconv3x3s2_wide(p, w, bias):
+    """vts_tconv3x3s2_wide: ConvTranspose2d(3, stride 2, padding 1, output_padding 1) of p [N, Cin, IH + 1, IW + 1] (the input with one zero
+    row / column appended) with w [Cin, Cout, 3, 3] -> [N, Cout, 2 IH, 2 IW]; out[y] sums in[i] w[k] over k = y + 1 - 2 i in 0..2, so
+    K_terms = Cin {1, 2, 2, 4} by output parity (the unit is per phase)."""
+    return _tconv_judge(p, w, bias, 3, 1, 2 * (p.shape[2] - 1), 2 * (p.shape[3] - 1))
+
+
+def conv4x4_wide_transposed(p, w, bias, out_hw):
+    """vts_conv4x4_wide (transposed = 1): the input adjoint of Conv2d(4, stride 2, padding 2).  p [N, Cin, PH, PW] is the output gradient
+    with one zero row / column appended, w [Cin, Cout, 4, 4] the layer's weight (its output channels first), out [N, Cout, OH, OW]:
+    out[i] = sum over (y, k) with 2 y + k - 2 = i of p[y] w[k]: 2 x 2 taps per element, K_terms = 4 Cin; with odd OH / OW the odd phase
+    is one row / column shorter."""
+    oh, ow = out_hw
+    assert 2 * (p.shape[2] - 1) >= oh + 1 and 2 * (p.shape[3] - 1) >= ow + 1
+    return _tconv_judge(p, w, bias, 4, 2, oh, ow)
+
+
+def wgrad_wide(dout, p, *, K, stride, dw0=None):
+    """vts_wgrad3x3_wide / vts_wgrad4x4_wide: dw[co, ci, ky, kx] = sum_{n, y, x} dout[n, co, y, x] p[n, ci, s y + ky, s x + kx]
+    (+ dw0 with accumulate); K_terms = N H W"""
+    dout, p = _f64(dout), _f64(p)
+    n, co, h, w = dout.shape
+    ci = p.shape[1]
+    assert p.shape[2] >= stride * (h - 1) + K and p.shape[3] >= stride * (w - 1) + K
+
+    def core(d, q):
+        d2 = d.transpose(0, 1).reshape(co, n * h * w)
+        dw = d.new_zeros(co, ci, K, K)
+        for ky in range(K):
+            for kx in range(K):
+                sl = q[:, :, ky:ky + (h - 1) * stride + 1:stride, kx:kx + (w - 1) * stride + 1:stride].transpose(0, 1).reshape(ci, n * h * w)
+                dw[:, :, ky, kx] = d2 @ sl.T
+        return dw
+    ref = core(dout, p)
+    unit = U * math.sqrt(n * h * w) * core(dout.abs(), p.abs())
+    if dw0 is not None:
+        o = _f64(dw0).view_as(ref)
+        ref, unit = ref + o, unit + U * o.abs()
+    return {"dw": (ref, unit)}
+
+
+def wtap_pack(w, A, B, sa, sb, T, flip):
+    """vts_w3x3_pack / vts_w4x4_pack (T = 9 | 16), the indexing formula itself: wt[(a T + t) Bp + b] = w[a sa + b sb + (flip ? T - 1 - t : t)]
+    for b < B, 0 for B <= b < Bp = B rounded up to 4.  A pure permutation: the result is exact in the input's own dtype."""
+    flat = w.detach().cpu().reshape(-1)
+    Bp = (B + 3) // 4 * 4
+    a = torch.arange(A).view(A, 1, 1)
+    t = torch.arange(T).view(1, T, 1)
+    b = torch.arange(B).view(1, 1, B)
+    wt = flat.new_zeros(A, T, Bp)
+    wt[:, :, :B] = flat[a * sa + b * sb + ((T - 1 - t) if flip else t)]
+    return wt.reshape(-1)
+
+
 def worst(got, ref, unit):
     """(max over elements of |got - ref| / unit, index of that element); inf where got is not finite.  An element whose unit is 0
     (an exact zero: masked out, empty sum) must match exactly."""

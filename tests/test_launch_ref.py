@@ -228,3 +228,137 @@ def test_elementwise_rule_catches_one_element_that_rel_l2_misses():
     assert rel_l2 <= 1e-5
     assert R.worst(bad, ref, unit)[0] > 8
     assert not math.isinf(R.worst(bad, ref, unit)[0])
+
+
+# ---- the judges of the GEMM-class "wide" ABI (tests/test_wide_family_gpu.py) ---------------------------------------------------
+
+def relerr(a, b):
+    return float((a - b).abs().max() / b.abs().max())
+
+
+@pytest.mark.parametrize("K,stride,shape", [(3, 1, (2, 5, 4, 6, 7)), (3, 2, (2, 3, 5, 4, 5)), (4, 1, (1, 4, 3, 5, 6)), (4, 2, (2, 3, 2, 5, 4))])
+@pytest.mark.parametrize("has_bias", [False, True])
+def test_conv_wide_judge_matches_conv2d(K, stride, shape, has_bias):
+    n, ci, co, oh, ow = shape
+    g = torch.Generator().manual_seed(K * 10 + stride)
+    ph, pw = stride * (oh - 1) + K + (stride - 1), stride * (ow - 1) + K + (stride - 1)     # stride 2: one row / column never read
+    p, w, b = rnd(g, n, ci, ph, pw), rnd(g, co, ci, K, K), (rnd(g, co) if has_bias else None)
+    ref, unit = R.conv_wide(p, w, b, K=K, stride=stride, out_hw=(oh, ow))["out"]
+    assert relerr(ref, F.conv2d(p, w, b, stride=stride)[:, :, :oh, :ow]) <= 1e-12
+    absref = F.conv2d(p.abs(), w.abs(), None if b is None else b.abs(), stride=stride)[:, :, :oh, :ow]
+    assert relerr(unit, R.U * math.sqrt(ci * K * K) * absref) <= 1e-12
+    if K == 3:
+        assert torch.equal(R.conv_wide(p, w, b, K=K, stride=stride)["out"][0], ref)         # the extent the 3 x 3 entries imply
+
+
+def test_conv_wide_judge_epilogues():
+    g = torch.Generator().manual_seed(5)
+    n, ci, co, h, w = 2, 3, 4, 5, 6
+    p, wt, b = rnd(g, n, ci, h + 2, w + 2), rnd(g, co, ci, 3, 3), rnd(g, co)
+    plain, unit0 = R.conv_wide(p, wt, b, K=3, stride=1)["out"]
+    ref, unit = R.conv_wide(p, wt, b, K=3, stride=1, epilogue="relu_pad")["out"]
+    assert ref.shape == (n, co, h + 2, w + 2)
+    assert torch.equal(ref, F.pad(F.relu(plain), (1, 1, 1, 1))) and torch.equal(unit, F.pad(unit0, (1, 1, 1, 1)))
+    assert (plain < 0).any() and (plain > 0).any()
+    mask, add = F.relu(rnd(g, n, co, h + 2, w + 2)), rnd(g, n, co, h + 2, w + 2)
+    assert (mask[:, :, 1:-1, 1:-1] == 0).any() and (mask[:, :, 0] > 0).any()
+    plain, unit0 = R.conv_wide(p, wt, None, K=3, stride=1)["out"]
+    for a in (None, add):
+        ref, unit = R.conv_wide(p, wt, None, K=3, stride=1, epilogue="mask_pad", mask=mask, add=a)["out"]
+        keep = F.pad((mask[:, :, 1:-1, 1:-1] > 0).to(D64), (1, 1, 1, 1))
+        want = (F.pad(plain, (1, 1, 1, 1)) + (0 if a is None else a)) * keep
+        assert relerr(ref, want) <= 1e-12
+        assert torch.equal(unit == 0, keep == 0)                  # masked elements and the border: exact zeros
+        assert (ref[keep == 0] == 0).all()
+        extra = 0 if a is None else R.U * math.sqrt(ci * 9) * a.abs() * keep
+        assert relerr(unit, F.pad(unit0, (1, 1, 1, 1)) * keep + extra) <= 1e-12
+
+
+@pytest.mark.parametrize("shape", [(2, 3, 4, 3, 5), (1, 5, 2, 4, 1)])
+@pytest.mark.parametrize("has_bias", [False, True])
+def test_tconv3x3s2_wide_judge_matches_conv_transpose2d(shape, has_bias):
+    n, ci, co, ih, iw = shape
+    g = torch.Generator().manual_seed(ih * 7 + iw)
+    x, w, b = rnd(g, n, ci, ih, iw), rnd(g, ci, co, 3, 3), (rnd(g, co) if has_bias else None)
+    ref, unit = R.tconv3x3s2_wide(F.pad(x, (0, 1, 0, 1)), w, b)["out"]
+    assert relerr(ref, F.conv_transpose2d(x, w, b, stride=2, padding=1, output_padding=1)) <= 1e-12
+    absref = F.conv_transpose2d(x.abs(), w.abs(), None if b is None else b.abs(), stride=2, padding=1, output_padding=1)
+    terms = torch.tensor([[1.0, 2.0], [2.0, 4.0]], dtype=D64).repeat(ih, iw) * ci        # by output parity (y % 2, x % 2)
+    assert relerr(unit, R.U * torch.sqrt(terms) * absref) <= 1e-12
+
+
+@pytest.mark.parametrize("shape", [(2, 3, 4, 6, 8), (1, 4, 3, 7, 5), (2, 2, 3, 4, 9), (1, 3, 2, 1, 2)])
+@pytest.mark.parametrize("has_bias", [False, True])
+def test_conv4x4_wide_transposed_judge_matches_autograd(shape, has_bias):
+    """the input gradient of Conv2d(4, stride 2, padding 2) by autograd; even and odd extents"""
+    n, ci, co, h, w = shape                    # the layer ci -> co on an h x w input
+    g = torch.Generator().manual_seed(h * 11 + w)
+    x = rnd(g, n, ci, h, w).requires_grad_(True)
+    wt, b = rnd(g, co, ci, 4, 4), (rnd(g, ci) if has_bias else None)
+    y = F.conv2d(x, wt, None, stride=2, padding=2)
+    cot = rnd(g, *y.shape)
+    (y * cot).sum().backward()
+    ref, unit = R.conv4x4_wide_transposed(F.pad(cot, (0, 1, 0, 1)), wt, b, (h, w))["out"]
+    want = x.grad + (0 if b is None else b.view(1, -1, 1, 1))
+    assert relerr(ref, want) <= 1e-12
+    xa = x.detach().clone().requires_grad_(True)
+    (F.conv2d(xa, wt.abs(), None, stride=2, padding=2) * cot.abs()).sum().backward()
+    absref = xa.grad + (0 if b is None else b.abs().view(1, -1, 1, 1))
+    assert relerr(unit, R.U * math.sqrt(4 * co) * absref) <= 1e-12
+
+
+@pytest.mark.parametrize("K,stride,shape", [(3, 1, (2, 3, 4, 5, 6)), (3, 2, (2, 4, 3, 3, 5)), (4, 1, (1, 2, 3, 4, 5)), (4, 2, (3, 3, 2, 4, 3))])
+@pytest.mark.parametrize("acc", [False, True])
+def test_wgrad_wide_judge_matches_autograd(K, stride, shape, acc):
+    n, ci, co, h, w = shape
+    g = torch.Generator().manual_seed(K + 3 * stride)
+    p = rnd(g, n, ci, stride * h + 2, stride * w + 2) if K == 3 else rnd(g, n, ci, stride * (h - 1) + 4, stride * (w - 1) + 4)
+    wt = rnd(g, co, ci, K, K).requires_grad_(True)
+    cot = rnd(g, n, co, h, w)
+    (F.conv2d(p, wt, stride=stride)[:, :, :h, :w] * cot).sum().backward()
+    dw0 = rnd(g, co, ci, K, K) if acc else None
+    ref, unit = R.wgrad_wide(cot, p, K=K, stride=stride, dw0=dw0)["dw"]
+    assert relerr(ref, wt.grad + (dw0 if acc else 0)) <= 1e-12
+    wa = wt.detach().clone().requires_grad_(True)
+    (F.conv2d(p.abs(), wa, stride=stride)[:, :, :h, :w] * cot.abs()).sum().backward()
+    assert relerr(unit, R.U * math.sqrt(n * h * w) * wa.grad + (R.U * dw0.abs() if acc else 0)) <= 1e-12
+
+
+def test_wtap_pack_formula_is_the_layers_weight():
+    """the packing formula with the (A, B, sa, sb, flip) of each mode (include/vts.h) reads back as the operator's weight"""
+    g = torch.Generator().manual_seed(9)
+    co, ci = 5, 7
+    w = rnd(g, co, ci, 3, 3)
+    fwd = R.wtap_pack(w, ci, co, 9, 9 * ci, 9, 0).view(ci, 9, 8)
+    assert torch.equal(fwd[:, :, :co], w.permute(1, 2, 3, 0).reshape(ci, 9, co)) and (fwd[:, :, co:] == 0).all()
+    adj = R.wtap_pack(w, co, ci, 9 * ci, 9, 9, 1).view(co, 9, 8)
+    assert torch.equal(adj[:, :, :ci], w.flip(2, 3).permute(0, 2, 3, 1).reshape(co, 9, ci)) and (adj[:, :, ci:] == 0).all()
+    w4 = rnd(g, co, ci, 4, 4)
+    s2 = R.wtap_pack(w4, co, ci, 16 * ci, 16, 16, 0).view(co, 16, 8)
+    assert torch.equal(s2[:, :, :ci], w4.permute(0, 2, 3, 1).reshape(co, 16, ci))
+
+
+def test_wide_judges_catch_one_dropped_product():
+    """one product missing from one element is more than 8 units of u sqrt(K) absref at the largest K of the wide-family table (the signal
+    is about 2^24 / K^1.5 units: the table keeps K below 2500, where that is still > 100)"""
+    import wide_family_cases as T
+
+    kmax = T.max_k_terms()
+    assert kmax <= 2500
+    ci = (kmax + 8) // 9
+    assert ci * 9 >= kmax
+    g = torch.Generator().manual_seed(11)
+    p = (torch.rand(1, ci, 5, 6, generator=g, dtype=D64) * 2 - 1).float()
+    w = ((torch.rand(4, ci, 3, 3, generator=g, dtype=D64) * 2 - 1) * math.sqrt(3.0 / (9 * ci))).float()
+    ref, unit = R.conv_wide(p, w, None, K=3, stride=1)["out"]
+    assert R.worst(ref.float(), ref, unit)[0] < 1.0                     # the rounding of the exact result to fp32 passes
+    smallest = []
+    for y, x in ((0, 0), (2, 3), (1, 2)):
+        prods = (p.double()[0, :, y:y + 3, x:x + 3] * w.double()[1]).abs()
+        c, ky, kx = [int(v) for v in torch.nonzero(prods == prods.flatten().sort()[0][prods.numel() // 2])[0]]
+        got = ref.clone()
+        got[0, 1, y, x] -= p.double()[0, c, y + ky, x + kx] * w.double()[1, c, ky, kx]      # the median-size product of that element dropped
+        ratio, at = R.worst(got, ref, unit)
+        assert at == (1 * 3 + y) * 4 + x
+        smallest.append(ratio)
+    assert min(smallest) > 8.0, smallest

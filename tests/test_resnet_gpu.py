@@ -425,7 +425,9 @@ def test_conv3x3_wide_forward_and_input_adjoint(shape):
 
 
 def test_conv3x3_wide_ksplit_small_map():
-    """few tiles: the k-split path with its deterministic reduction"""
+    """few tiles: a k-split path with its deterministic reduction.  8 x 16 = 128 pixels is a flat map, so this is the flattened kernel's
+    k-split (16 slices); the tiled kernels' k-split is judged in tests/test_wide_family_gpu.py"""
+    from vts import lib as L
     from vts import ops
     dev = _dev()
     n, ci, co, h, w = 1, 256, 128, 8, 16
@@ -434,6 +436,7 @@ def test_conv3x3_wide_ksplit_small_map():
     b = detrand.uniform((co,), 22, "b")
     out = torch.full((n, co, h, w), float("nan"), device=dev)
     ops.conv3x3_wide(p.to(dev), ops.w3x3_pack(wt.to(dev), "conv_fwd"), b.to(dev), out)
+    assert L.load().vts_last_kernel().decode() == "conv_flat_kernel<8, 9>+ksplit"
     assert rel(out, F.conv2d(p, wt, b)) < 1e-5
     out2 = torch.empty_like(out)
     ops.conv3x3_wide(p.to(dev), ops.w3x3_pack(wt.to(dev), "conv_fwd"), b.to(dev), out2)

@@ -878,6 +878,64 @@ int vts_spectral_norm(const float* w, float* u, float* v, int Co, int K, int tra
 int vts_spectral_norm_bwd(const float* g, const float* w_sn, const float* u, const float* v, const float* sigma, int Co, int K, float* dw,
                           int accumulate, float* ws, int64_t ws_floats, void* stream);
 
+/* ---- CLIP ViT image tower, forward only (csrc/vts_vit.hip) -------------------------------------------------------------------------------
+ * skitG's style code: the reference runs a frozen CLIP ViT-B/32 image encoder in half precision on the masked visual image at every
+ * forward (reference models/skitG_model.py:484-489, 704-724, 1294-1296).  Precision regime of every entry below: weights and GEMM inputs
+ * are IEEE fp16 (passed as uint16_t bit patterns), every matrix product runs on v_mfma_f32_16x16x32_f16 with fp32 accumulation, and the
+ * residual stream, LayerNorm statistics, softmax, biases and epilogues are evaluated in fp32.  Repeats are bit-identical (no float atomics;
+ * split-K partials are reduced in a fixed order).
+ *
+ * vts_gemm_f16: C[M x N] = epilogue(A[M x K] W[N x K]^T + bias[N]), A / W / bias fp16 row-major (bias NULL: none).
+ *   epilogue VTS_GEMM_NONE; VTS_GEMM_QUICKGELU: v * sigmoid(1.702 v); VTS_GEMM_RESIDUAL: out[m][n] += v (out fp32, read and written).
+ *   out_f16 0: out is float [M x N]; 1: out is fp16 [M x N] (round to nearest even; not with VTS_GEMM_RESIDUAL).
+ *   Any M >= 1; K % 32 == 0 and N % 16 == 0, VTS_ERR_UNSUPPORTED otherwise.  A workgroup owns 32 output features over all M rows, so each
+ *   weight element is fetched from memory once per call; narrow N splits K over up to 8 workgroups whose partials (ws,
+ *   vts_gemm_f16_ws_floats(M, N, K) floats; 0 means ws may be NULL) a second launch sums in split order.
+ * vts_layernorm_rows: y[r] = (x[r] - mean) / sqrt(var + eps) * gamma + beta over rows of D fp32 values, x row r at x + r * x_stride
+ *   (floats), y row r at r * D; biased variance, two-pass fp32 statistics; gamma / beta fp16 [D]; out_f16 as above.
+ * vts_vit_attention: nn.MultiheadAttention's unmasked self-attention core on the packed projection qkv fp16 [B*T][3*heads*64]
+ *   (q | k | v, each heads x 64): out[b*T + t][h*64 + :] = softmax(q_h k_h^T / 8) v_h, fp16 [B*T][heads*64].  Scores and softmax fp32,
+ *   one workgroup per (image, head), one wave per 16 queries.  Head dimension 64 and 1 <= T <= 64 only (ViT-B/32 at 224^2: T = 50); VTS_ERR_UNSUPPORTED otherwise.
+ * vts_clip_preprocess: CLIP's transform ToPILImage -> Resize(224, BICUBIC) -> CenterCrop(224) -> ToTensor -> Normalize -> .half() of an
+ *   fp32 [N][3][H][W] image, bit-exact with the host chain: byte = trunc(x * 255) mod 256 (ToPILImage's mul(255).byte(), which wraps
+ *   negative values), Pillow's two 22-bit fixed-point passes (horizontal to uint8, then vertical to uint8) and a 3 x 256 lookup table
+ *   for /255, -mean, /std and the fp16 rounding.  The host supplies the tables (vts/ops.py:clip_preprocess_tables builds and caches them
+ *   per input size): hb / vb int32 [224][2] = first source column (row) and tap count of cropped output column (row) j, hk / vk int32
+ *   [224][hks] / [224][vks] the taps, lut fp16 [3][256]; tmp is N*3*H*224 bytes for the horizontal pass.  out fp16 [N][3][224][224].
+ *
+ * vts_clip_visual_forward: CLIP's VisionTransformer.forward (clip/model.py:206-240 of the published package) as ONE call --
+ *   conv1 (patch x patch, stride patch, no bias) as gather + GEMM, class embedding ++ tokens + positional embedding, ln_pre,
+ *   `layers` x [x += out_proj(attention(in_proj(ln_1(x))));  x += c_proj(QuickGELU(c_fc(ln_2(x))))], ln_post on the class token, @ proj.
+ *   x      fp16 [N][3][resolution][resolution] (vts_clip_preprocess's output), out float [N][output_dim]
+ *   w      one flat fp16 buffer, segments in this order (T = (resolution/patch)^2 + 1, W = width):
+ *            conv1.weight [W][3*patch*patch], class_embedding [W], positional_embedding [T][W], ln_pre.weight [W], ln_pre.bias [W],
+ *            per layer: ln_1.weight [W], ln_1.bias [W], attn.in_proj_weight [3W][W], attn.in_proj_bias [3W], attn.out_proj.weight [W][W],
+ *                       attn.out_proj.bias [W], ln_2.weight [W], ln_2.bias [W], mlp.c_fc.weight [4W][W], mlp.c_fc.bias [4W],
+ *                       mlp.c_proj.weight [W][4W], mlp.c_proj.bias [W],
+ *            ln_post.weight [W], ln_post.bias [W], proj TRANSPOSED [output_dim][W];   vts_clip_visual_weight_halfs(cfg) halfs in all
+ *   ws     vts_clip_visual_forward_ws_floats(cfg, N) floats (-1 on a bad config), 16-byte aligned
+ *   Requires width == 64 * heads, T <= 64, width % 32 == 0, width <= 1024, output_dim % 16 == 0, resolution % patch == 0 and (3*patch*patch) % 32 == 0
+ *   (the text tower and the other CLIP image towers are out of scope: VTS_ERR_UNSUPPORTED).  No allocation, no host synchronisation,
+ *   every launch on `stream`: the call can be captured into a graph. */
+#define VTS_GEMM_NONE 0
+#define VTS_GEMM_QUICKGELU 1
+#define VTS_GEMM_RESIDUAL 2
+typedef struct vts_clip_visual_cfg {
+  int width, layers, heads, patch, resolution, output_dim;
+} vts_clip_visual_cfg;
+int64_t vts_gemm_f16_ws_floats(int M, int N, int K);
+int vts_gemm_f16(const uint16_t* A, const uint16_t* W, const uint16_t* bias, int M, int N, int K, int epilogue, void* out, int out_f16,
+                 float* ws, int64_t ws_floats, void* stream);
+int vts_layernorm_rows(const float* x, int64_t x_stride, int rows, int D, const uint16_t* gamma, const uint16_t* beta, float eps, void* y,
+                       int out_f16, void* stream);
+int vts_vit_attention(const uint16_t* qkv, int B, int T, int heads, int head_dim, uint16_t* out, void* stream);
+int vts_clip_preprocess(const float* x, int N, int H, int W, const int* hb, const int* hk, int hks, const int* vb, const int* vk, int vks,
+                        const uint16_t* lut, uint8_t* tmp, uint16_t* out, void* stream);
+int64_t vts_clip_visual_weight_halfs(const vts_clip_visual_cfg* cfg);
+int64_t vts_clip_visual_forward_ws_floats(const vts_clip_visual_cfg* cfg, int N);
+int vts_clip_visual_forward(const vts_clip_visual_cfg* cfg, const uint16_t* w, const uint16_t* x, int N, float* out, float* ws,
+                            int64_t ws_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

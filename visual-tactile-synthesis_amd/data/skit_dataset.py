@@ -14,10 +14,11 @@ Not kept:
       material with tactile data; the parent's default (True: contact masks are loaded) is what the golden vectors were generated with
       (oracle/make_dataset_golden.py sets the attribute) and what this class does;
 Added: a precomputed style code per material (<material folder>/style_code.npy) travels as the batch key `style_code` (the reference
-encodes the visual image with CLIP inside the model, skitG_model.py:484-489; CLIP's weights cannot exist offline).
+encodes the visual image with CLIP inside the model, skitG_model.py:484-489; a batch without the key has its code computed by the
+model's own CLIP tower, models/clip_visual.py, on stand-in weights unless --clip_weights names the published ones).
 Not kept (continued):
-    * `use_external_test_input` (:113-141: a sketch of one material with the style IMAGE of another, for the CLIP style encoder): the style
-      code is an input of this package (no CLIP weights offline), so the style image has no consumer -- raises.
+    * `use_external_test_input` (:113-141: a sketch of one material with the style IMAGE of another, for the CLIP style encoder): out of scope
+      of this dataset class -- raises.  (The MODEL takes batch keys `style_I` / `style_M` and encodes them: models/skitG_model.py.)
 """
 import ntpath
 import os
@@ -41,8 +42,9 @@ class SkitDataset(SingleSkitDataset):
         self.data_len = opt.data_len if hasattr(opt, "data_len") else default_len
         self.is_train = opt.is_train
         if getattr(opt, "use_external_test_input", False):
-            raise NotImplementedError("--use_external_test_input: the style IMAGE of a second material feeds the CLIP style encoder, which is "
-                                      "not built (the style code is a batch input: key `style_code`)")
+            raise NotImplementedError("--use_external_test_input: pairing a sketch with the style IMAGE of a second material is not built in this "
+                                      "dataset class (out of scope); SKITGModel.set_input does encode batch keys `style_I` / `style_M` when a caller "
+                                      "supplies them, and a batch key `style_code` keeps precedence")
         materials = list(getattr(opt, "material_list", []))
         if not materials:
             raise ValueError("--dataset_mode skit needs --material_list")

@@ -270,7 +270,8 @@ class SinSKITGModel(BaseModel):
             raise NotImplementedError(
                 "epoch %d >= --vision_aided_warmup_epoch %d: from here on the reference adds the CLIP vision-aided discriminator terms "
                 "(models/sinskitG_model.py:1393-1398, 1719-1720; third-party package vision_aided_loss + CLIP ViT-B/32 weights, neither "
-                "available offline).  They are not built on the HIP path: continue with --use_vision_aided_loss False (note that the "
+                "available offline).  They are not built on the HIP path (the CLIP image tower of models/clip_visual.py is forward only: D3 needs "
+                "its backward and CLIP's multi-level heads, out of scope): continue with --use_vision_aided_loss False (note that the "
                 "reference never hands netD3's head to an optimizer nor saves it, so the term is a frozen random projection of frozen "
                 "CLIP features)." % (epoch, opt.vision_aided_warmup_epoch))
 
@@ -436,6 +437,17 @@ class SinSKITGModel(BaseModel):
         return dict(real_T=real_T, masks=views["masks"], NT=nt, offx=views["offx"], offy=views["offy"], img=views["img"],
                     coords=np.asarray(T_coords))
 
+    def _tile_style_code(self, phase, n, h, w):
+        G = self.netG
+        if getattr(G, "use_style", False) and getattr(G, "style_mapping", "") == "tile":
+            # the tiled style code (networks.py:1600-1623) depends on the batch only: tiled here, once per batch, into persistent buffers
+            self._style_tiles = {}
+            for i in range(G.num_downs - G.num_layer_style_code, G.num_downs):
+                hh, ww = h >> (i + 1), w >> (i + 1)
+                t = self._buf("%s_style_tile%d" % (phase, i), (n, self.style_code.shape[1], hh, ww))
+                t.copy_(self.style_code.to(torch.float32)[:, :, None, None].expand(-1, -1, hh, ww))
+                self._style_tiles[i] = t
+
     def set_input(self, input, phase="train", timing=False, verbose=False):
         self.data_phase = phase
         self.name = input.get("name")
@@ -520,15 +532,7 @@ class SinSKITGModel(BaseModel):
         self._style_tiles = None
         if "style_code" in input:
             self.style_code = self._load(phase + "_style", input["style_code"])
-            G = self.netG
-            if getattr(G, "use_style", False) and getattr(G, "style_mapping", "") == "tile":
-                # the tiled style code (networks.py:1600-1623) depends on the batch only: tiled here, once per batch, into persistent buffers
-                self._style_tiles = {}
-                for i in range(G.num_downs - G.num_layer_style_code, G.num_downs):
-                    hh, ww = h >> (i + 1), w >> (i + 1)
-                    t = self._buf("%s_style_tile%d" % (phase, i), (n, self.style_code.shape[1], hh, ww))
-                    t.copy_(self.style_code.to(torch.float32)[:, :, None, None].expand(-1, -1, hh, ww))
-                    self._style_tiles[i] = t
+            self._tile_style_code(phase, n, h, w)
         self.train_set = self.val_set = None
         if "T_images" in input and len(input["T_images"]) > 0:
             self.train_set = self._patch_set(phase + "_tr", input["T_images"], input["I_masks"], input["T_coords"])

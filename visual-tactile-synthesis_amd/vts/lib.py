@@ -133,6 +133,11 @@ class PatchJob(C.Structure):
                 ("dst_C", C.c_int), ("dst_c0", C.c_int), ("fill", C.c_float)]
 
 
+class ClipVisualCfg(C.Structure):
+    """vts_clip_visual_cfg (include/vts.h): the CLIP image tower's architecture"""
+    _fields_ = [("width", C.c_int), ("layers", C.c_int), ("heads", C.c_int), ("patch", C.c_int), ("resolution", C.c_int), ("output_dim", C.c_int)]
+
+
 class NormBwdDesc(C.Structure):
     _fields_ = [
         ("dy", C.c_void_p), ("x", C.c_void_p), ("nstride", C.c_int64), ("N", C.c_int), ("C", C.c_int), ("HW", C.c_int),
@@ -158,6 +163,8 @@ SYMBOLS = [
     "vts_u8_expand", "vts_unet_forward", "vts_unet_forward_ws_floats", "vts_patchgan_forward", "vts_patchgan_forward_ws_floats", "vts_msd_forward", "vts_msd_forward_ws_floats", "vts_unet_backward", "vts_unet_backward_ws_floats", "vts_patchgan_backward", "vts_patchgan_backward_ws_floats", "vts_msd_backward", "vts_msd_backward_ws_floats", "vts_allreduce_slice_plan", "vts_comm_unique_id", "vts_comm_init", "vts_allreduce_flat_async", "vts_allreduce_flat_wait", "vts_comm_destroy",
     "vts_spade_modulate", "vts_spade_modulate_bwd_ws_floats", "vts_spade_modulate_bwd", "vts_nearest_resize", "vts_nearest_resize_bwd", "vts_nearest_up2", "vts_nearest_up2_bwd",
     "vts_spectral_norm_ws_floats", "vts_spectral_norm", "vts_spectral_norm_bwd", "vts_tanh_bwd", "vts_spade_eval_stats",
+    "vts_gemm_f16_ws_floats", "vts_gemm_f16", "vts_layernorm_rows", "vts_vit_attention", "vts_clip_preprocess", "vts_clip_visual_weight_halfs",
+    "vts_clip_visual_forward_ws_floats", "vts_clip_visual_forward",
 ]
 
 
@@ -215,6 +222,12 @@ def load():
     lib.vts_spade_modulate_bwd_ws_floats.restype = C.c_int64
     lib.vts_spectral_norm_ws_floats.argtypes = [C.c_int, C.c_int]
     lib.vts_spectral_norm_ws_floats.restype = C.c_int64
+    lib.vts_gemm_f16_ws_floats.argtypes = [C.c_int] * 3
+    lib.vts_gemm_f16_ws_floats.restype = C.c_int64
+    lib.vts_clip_visual_weight_halfs.argtypes = [C.POINTER(ClipVisualCfg)]
+    lib.vts_clip_visual_weight_halfs.restype = C.c_int64
+    lib.vts_clip_visual_forward_ws_floats.argtypes = [C.POINTER(ClipVisualCfg), C.c_int]
+    lib.vts_clip_visual_forward_ws_floats.restype = C.c_int64
     vp, i, i64, f = C.c_void_p, C.c_int, C.c_int64, C.c_float
     sig = {
         "vts_conv4x4": [C.POINTER(ConvDesc), vp],
@@ -323,6 +336,11 @@ def load():
         "vts_spade_eval_stats": [vp, vp, f, i, i, vp, vp, vp],
         "vts_spectral_norm": [vp, vp, vp, i, i, i, f, vp, vp, vp, i64, vp],
         "vts_spectral_norm_bwd": [vp, vp, vp, vp, vp, i, i, vp, i, vp, i64, vp],
+        "vts_gemm_f16": [vp, vp, vp, i, i, i, i, vp, i, vp, i64, vp],
+        "vts_layernorm_rows": [vp, i64, i, i, vp, vp, f, vp, i, vp],
+        "vts_vit_attention": [vp, i, i, i, i, vp, vp],
+        "vts_clip_preprocess": [vp, i, i, i, vp, vp, i, vp, vp, i, vp, vp, vp, vp],
+        "vts_clip_visual_forward": [C.POINTER(ClipVisualCfg), vp, vp, i, vp, vp, i64, vp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)

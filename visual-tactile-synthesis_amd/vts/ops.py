@@ -4,6 +4,7 @@
 per-(n,c) scale/shift produced by vts_norm_stats (see include/vts.h, vts_operand).
 """
 import ctypes as C
+import math
 import os
 from . import tune
 
@@ -1718,3 +1719,158 @@ def spade_eval_stats(running_mean, running_var, n, eps=1e-5):
     _run("spade_eval_stats", 8.0 * (n + 1) * c, 0.0, L.load().vts_spade_eval_stats, running_mean.data_ptr(), running_var.data_ptr(), eps, n, c,
          st[0].data_ptr(), st[1].data_ptr(), L.stream())
     return st[0], st[1]
+
+
+# ---- CLIP ViT image tower (include/vts.h "CLIP ViT image tower", csrc/vts_vit.hip): skitG's style encoder, forward only ----
+GEMM_EPILOGUES = {"none": 0, "quickgelu": 1, "residual": 2}
+
+
+def gemm_f16(a, w, bias=None, epilogue="none", out=None, out_dtype=torch.float32):
+    """epilogue(a [M, K] @ w [N, K]^T + bias [N]) on the f16 MFMAs with fp32 accumulation; a / w / bias fp16.  `residual` adds into the
+    fp32 `out`; otherwise out is fp32 or fp16 (`out_dtype`)."""
+    m, k = a.shape
+    n = w.shape[0]
+    assert a.dtype == w.dtype == torch.float16 and w.shape[1] == k and a.is_contiguous() and w.is_contiguous()
+    assert bias is None or (bias.dtype == torch.float16 and bias.numel() == n and bias.is_contiguous())
+    if out is None:
+        assert epilogue != "residual", "the residual epilogue adds into `out`"
+        out = torch.empty(m, n, dtype=out_dtype, device=a.device)
+    assert tuple(out.shape) == (m, n) and out.is_contiguous() and out.dtype in (torch.float32, torch.float16)
+    lib = L.load()
+    nws = lib.vts_gemm_f16_ws_floats(m, n, k)
+    ws = workspace(nws, a.device) if nws else None
+    _run("gemm_f16", 2.0 * (m * k + n * k) + out.element_size() * m * n, 2.0 * m * n * k, lib.vts_gemm_f16, a.data_ptr(), w.data_ptr(), L.ptr(bias),
+         m, n, k, GEMM_EPILOGUES[epilogue], out.data_ptr(), int(out.dtype == torch.float16), L.ptr(ws), nws, L.stream())
+    return out
+
+
+def layernorm_rows(x, gamma, beta, eps=1e-5, out_dtype=torch.float32):
+    """nn.LayerNorm over the last dimension of fp32 x [rows, D] (fp32 statistics); gamma / beta fp16 [D]; output fp32 or fp16"""
+    rows, d = x.shape
+    assert x.dtype == torch.float32 and x.stride(1) == 1 and gamma.dtype == beta.dtype == torch.float16 and gamma.numel() == beta.numel() == d
+    y = torch.empty(rows, d, dtype=out_dtype, device=x.device)
+    _run("layernorm_rows", 4.0 * rows * d + y.element_size() * rows * d, 8.0 * rows * d, L.load().vts_layernorm_rows, x.data_ptr(), x.stride(0), rows, d,
+         gamma.data_ptr(), beta.data_ptr(), eps, y.data_ptr(), int(out_dtype == torch.float16), L.stream())
+    return y
+
+
+def vit_attention(qkv, batch, tokens, heads):
+    """softmax(q k^T / sqrt(hd)) v per (image, head) on the packed fp16 projection qkv [batch * tokens, 3 * heads * hd] -> fp16
+    [batch * tokens, heads * hd]; head dimension 64 and tokens <= 64 only (the library reports anything else)"""
+    assert qkv.dtype == torch.float16 and qkv.is_contiguous() and qkv.shape[0] == batch * tokens and qkv.shape[1] % (3 * heads) == 0
+    hd = qkv.shape[1] // (3 * heads)
+    out = torch.empty(batch * tokens, heads * hd, dtype=torch.float16, device=qkv.device)
+    _run("vit_attention", 2.0 * (qkv.numel() + out.numel()), 4.0 * batch * heads * tokens * tokens * hd, L.load().vts_vit_attention, qkv.data_ptr(),
+         batch, tokens, heads, hd, out.data_ptr(), L.stream())
+    return out
+
+
+CLIP_MEAN, CLIP_STD = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)
+_clip_tables = {}
+
+
+def _bicubic(x):
+    """Pillow's bicubic filter (a = -0.5), in its own evaluation order"""
+    a = -0.5
+    x = abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def _resample_taps(in_size, out_size, crop0):
+    """Pillow's precompute_coeffs + normalize_coeffs_8bpc for output positions crop0 .. crop0 + 223: (bounds [224, 2], taps [224, ksize]) int32"""
+    scale = in_size / out_size
+    fscale = max(scale, 1.0)
+    support = 2.0 * fscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    bounds, taps = [], []
+    for xx in range(crop0, crop0 + 224):
+        center = (xx + 0.5) * scale
+        ss = 1.0 / fscale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), in_size) - xmin
+        k = [_bicubic((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        ww = sum(k)      # (left to right, as the C loop adds them)
+        if ww != 0.0:
+            k = [v / ww for v in k]
+        row = [int(-0.5 + v * (1 << 22)) if v < 0 else int(0.5 + v * (1 << 22)) for v in k]
+        bounds.append((xmin, xmax))
+        taps.append(row + [0] * (ksize - xmax))
+    return torch.tensor(bounds, dtype=torch.int32), torch.tensor(taps, dtype=torch.int32)
+
+
+def clip_preprocess_tables(h, w, device):
+    """The host's share of vts_clip_preprocess for an [.., h, w] input, cached per size: Pillow's fixed-point bicubic taps of
+    Resize(224) (shorter side to 224, longer to int(224 * long / short)) restricted to CenterCrop(224)'s window, and the 3 x 256 table of
+    ToTensor -> Normalize(CLIP mean, std) -> .half() filled with torch's own arithmetic."""
+    key = (h, w, str(device))
+    t = _clip_tables.get(key)
+    if t is None:
+        if w <= h:
+            ow, oh = 224, int(224 * h / w)
+        else:
+            oh, ow = 224, int(224 * w / h)
+        top, left = int(round((oh - 224) / 2.0)), int(round((ow - 224) / 2.0))
+        hb, hk = _resample_taps(w, ow, left)
+        vb, vk = _resample_taps(h, oh, top)
+        byte = torch.arange(256, dtype=torch.uint8).to(torch.float32).div(255)[None, :].repeat(3, 1)
+        lut = byte.sub_(torch.tensor(CLIP_MEAN, dtype=torch.float32)[:, None]).div_(torch.tensor(CLIP_STD, dtype=torch.float32)[:, None]).half()
+        t = _clip_tables[key] = tuple(v.contiguous().to(device) for v in (hb, hk, vb, vk, lut))
+    return t
+
+
+def clip_preprocess(x, out=None):
+    """CLIP's transform (ToPILImage, Resize(224, BICUBIC), CenterCrop(224), ToTensor, Normalize, .half()) of an fp32 [N, 3, H, W] image on
+    the device, bit-exact with the host chain (include/vts.h: vts_clip_preprocess) -> fp16 [N, 3, 224, 224]"""
+    n, c, h, w = x.shape
+    assert c == 3 and x.dtype == torch.float32 and x.is_contiguous()
+    hb, hk, vb, vk, lut = clip_preprocess_tables(h, w, x.device)
+    if out is None:
+        out = torch.empty(n, 3, 224, 224, dtype=torch.float16, device=x.device)
+    assert tuple(out.shape) == (n, 3, 224, 224) and out.dtype == torch.float16 and out.is_contiguous()
+    tmp = workspace((n * 3 * h * 224 + 3) // 4, x.device)
+    _run("clip_preprocess", 4.0 * x.numel() + 2.0 * n * 3 * h * 224 + 2.0 * out.numel(), 0.0, L.load().vts_clip_preprocess, x.data_ptr(), n, h, w,
+         hb.data_ptr(), hk.data_ptr(), hk.shape[1], vb.data_ptr(), vk.data_ptr(), vk.shape[1], lut.data_ptr(), tmp.data_ptr(), out.data_ptr(), L.stream())
+    return out
+
+
+def clip_visual_cfg(width, layers, heads, patch, resolution, output_dim):
+    return L.ClipVisualCfg(width, layers, heads, patch, resolution, output_dim)
+
+
+def clip_visual_weight_halfs(cfg):
+    n = L.load().vts_clip_visual_weight_halfs(C.byref(cfg))
+    if n < 0:
+        raise RuntimeError("vts_clip_visual_weight_halfs: %s" % L.load().vts_last_error().decode())
+    return n
+
+
+def clip_visual_forward_ws_floats(cfg, n):
+    nws = L.load().vts_clip_visual_forward_ws_floats(C.byref(cfg), n)
+    if nws < 0:
+        raise RuntimeError("vts_clip_visual_forward: %s" % L.load().vts_last_error().decode())
+    return nws
+
+
+def clip_visual_forward(cfg, wbuf, x, out=None, ws=None):
+    """CLIP's VisionTransformer.forward as one C call: x fp16 [N, 3, res, res], wbuf the flat fp16 weight buffer (include/vts.h layout)
+    -> fp32 [N, output_dim].  `ws`: a caller-owned fp32 scratch (a captured graph keeps its own), else the shared workspace."""
+    lib = L.load()
+    n = x.shape[0]
+    assert x.dtype == wbuf.dtype == torch.float16 and x.is_contiguous() and wbuf.is_contiguous()
+    assert tuple(x.shape) == (n, 3, cfg.resolution, cfg.resolution), tuple(x.shape)
+    nws = clip_visual_forward_ws_floats(cfg, n)
+    assert wbuf.numel() == clip_visual_weight_halfs(cfg), (wbuf.numel(), clip_visual_weight_halfs(cfg))
+    if ws is None:
+        ws = workspace(nws, x.device)
+    if out is None:
+        out = torch.empty(n, cfg.output_dim, dtype=torch.float32, device=x.device)
+    assert tuple(out.shape) == (n, cfg.output_dim) and out.dtype == torch.float32 and out.is_contiguous()
+    t = (cfg.resolution // cfg.patch) ** 2 + 1
+    flops = 2.0 * n * ((t - 1) * cfg.width * 3 * cfg.patch ** 2 + cfg.layers * t * (12 * cfg.width ** 2 + 2 * t * cfg.width) + cfg.width * cfg.output_dim)
+    _run("clip_visual_forward", 2.0 * (wbuf.numel() + x.numel()), flops, lib.vts_clip_visual_forward, C.byref(cfg), wbuf.data_ptr(), x.data_ptr(), n,
+         out.data_ptr(), ws.data_ptr(), ws.numel(), L.stream())
+    return out

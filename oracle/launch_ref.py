@@ -1,5 +1,5 @@
-"""Float64 judge of the C ABI's conv / weight-gradient / normalisation semantics, written from the formulas in include/vts.h (not from
-the kernels).  Checker only: the product never imports it.
+"""Float64 judge of the C ABI's conv / weight-gradient / normalisation semantics and of the step's glue kernels (loss, optimiser,
+pyramid, patches, post-processing, augmentation, staging, sampler), written from the formulas in include/vts.h (not from the kernels).  Checker only: the product never imports it.
 
 Every function returns {name: (ref, unit)} with float64 tensors: `ref` the exact value, `unit` the elementwise error scale of an
 fp32 evaluation, u * sqrt(K) * absref, where u = 2^-24, K is the number of products summed into the element and absref is the same
@@ -438,6 +438,413 @@ def wtap_pack(w, A, B, sa, sb, T, flip):
     wt = flat.new_zeros(A, T, Bp)
     wt[:, :, :B] = flat[a * sa + b * sb + ((T - 1 - t) if flip else t)]
     return wt.reshape(-1)
+
+
+# ---- the step's glue kernels (csrc/vts_ops.hip): loss, optimiser, pyramid, patch, post-processing, augmentation, staging, sampler ----------
+# Written from the formulas of include/vts.h and the reference semantics.  Arithmetic outputs: unit = u * r * absref, r = the number of
+# fp32 roundings in the header formula (a libm call counts 2, a constant the caller passes as a float is exact), absref = the same
+# expression with every term in absolute value -- a cancellation (1 - beta^t, x - mean) is therefore carried by absref, not by r.  Sums:
+# u * sqrt(K) * absref.  Scalars are taken as the fp32 values the C ABI receives (_f32).  Data movement and integer results are exact:
+# the judges return them in the output's own dtype and the tests compare bitwise.
+
+def _f32(v):
+    """the value a C float argument carries"""
+    return float(torch.tensor(float(v), dtype=torch.float32))
+
+
+def _pool_windows(x):
+    """(sum of the valid taps, their number [OH, OW]) of AvgPool2d(3, 2, 1, count_include_pad=False) windows"""
+    h, w = x.shape[-2:]
+    oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    p = torch.nn.functional.pad(x, (1, 2 * ow - w, 1, 2 * oh - h))      # rows -1 .. 2 OH - 1
+    one = torch.nn.functional.pad(x.new_ones(h, w), (1, 2 * ow - w, 1, 2 * oh - h))
+    s, cnt = x.new_zeros(x.shape[:-2] + (oh, ow)), x.new_zeros(oh, ow)
+    for dy in range(3):
+        for dx in range(3):
+            s = s + p[..., dy:dy + 2 * oh:2, dx:dx + 2 * ow:2]
+            cnt = cnt + one[dy:dy + 2 * oh:2, dx:dx + 2 * ow:2]
+    return s, cnt
+
+
+def avgpool3s2(x):
+    """vts_avgpool3s2: y[oy, ox] = mean of the taps x[2 oy + dy, 2 ox + dx], dy, dx in -1..1, that lie inside the map.  K = taps (<= 9)
+    addends and one division: unit = u (sqrt(K) + 1) absref."""
+    x = _f64(x)
+    s, cnt = _pool_windows(x)
+    a, _ = _pool_windows(x.abs())
+    return {"y": (s / cnt, U * (torch.sqrt(cnt) + 1) * a / cnt)}
+
+
+def _pool_adjoint(g, h, w):
+    """sum over the windows covering (y, x) of g[oy, ox] / taps(oy, ox)"""
+    oh, ow = g.shape[-2:]
+    assert (oh, ow) == ((h - 1) // 2 + 1, (w - 1) // 2 + 1)
+    _, cnt = _pool_windows(g.new_ones(h, w))
+    q = g / cnt
+    buf = g.new_zeros(g.shape[:-2] + (2 * oh + 1, 2 * ow + 1))            # rows -1 .. 2 OH - 1
+    for dy in range(3):
+        for dx in range(3):
+            buf[..., dy:dy + 2 * oh:2, dx:dx + 2 * ow:2] += q
+    return buf[..., 1:1 + h, 1:1 + w]
+
+
+def avgpool3s2_bwd(dy, h, w, dx0=None):
+    """vts_avgpool3s2_bwd: dx[y, x] (+)= sum over the (<= 4) windows that cover (y, x) of dy[oy, ox] / taps(oy, ox): one division per term,
+    sqrt(4) for the sum (r = 3), one more rounding for the accumulate"""
+    g = _f64(dy)
+    ref, a = _pool_adjoint(g, h, w), _pool_adjoint(g.abs(), h, w)
+    unit = 3 * U * a
+    if dx0 is not None:
+        o = _f64(dx0)
+        ref, unit = ref + o, unit + U * (o.abs() + a)
+    return {"dx": (ref, unit)}
+
+
+def _softplus(x):
+    return torch.where(x > 20, x, torch.log1p(torch.exp(torch.clamp(x, max=20.0))))      # F.softplus, threshold 20
+
+
+GAN_L_ROUNDINGS = {0: 4, 1: 3, 2: 7, 3: 0, 4: 1, 5: 11}
+GAN_G_ROUNDINGS = {0: 7, 1: 4, 2: 8, 3: 3, 4: 3, 5: 15}
+
+
+def ganloss(pred, mode, real, label, coeff, grad_coeff, workgroups=1):
+    """vts_ganloss, kernel modes 0-5 (include/vts.h).  per element l, g = dl/dp:
+      0 nonsaturating  l = softplus(-+p)                       g = -+sigmoid(-+p)         (upper sign: target real)
+      1 lsgan          l = (p - label)^2                       g = 2 (p - label)
+      2 vanilla        l = max(p, 0) - p label + log1p(exp(-|p|))   g = sigmoid(p) - label
+      3 wgan           l = -+p                                 g = -+1
+      4 hinge          l = max(1 -+ p, 0)                      g = -+[1 -+ p > 0]
+      5 vanilla on q = sigmoid(p):  l = q - q label + log1p(exp(-q)),  g = (sigmoid(q) - label) q (1 - q)
+    "loss" = coeff / total * sum l: what one call adds to the slot, in units of 1.0 (slot / 2^40 minus its start value); K = total
+    addends: unit = u (sqrt(K) + r_l + 1) coeff / total * sum absref_l + workgroups * 2^-41 (r_l: roundings of one l, 1: the fp32
+    1 / total, 2^-41: each workgroup's rounding to fixed point).  "dpred" = grad_coeff / total * g: r_g roundings, which include 1 / total
+    and the two products (GAN_L_ROUNDINGS / GAN_G_ROUNDINGS count them from the lines above: exp, log1p 2 each)."""
+    p = _f64(pred).reshape(-1)
+    label, coeff, grad_coeff = _f32(label), _f32(coeff), _f32(grad_coeff)
+    total = p.numel()
+    sg = -1.0 if real else 1.0
+    sig = torch.sigmoid
+    if mode == 0:
+        l, g = _softplus(sg * p), sg * torch.where(sg * p > 20, torch.ones_like(p), sig(sg * p))      # F.softplus: identity above 20
+        la, ga = l, g.abs()
+    elif mode == 1:
+        l, g = (p - label) ** 2, 2 * (p - label)
+        la, ga = (p.abs() + abs(label)) ** 2, 2 * (p.abs() + abs(label))
+    elif mode == 2:
+        l, g = p.clamp_min(0) - p * label + torch.log1p(torch.exp(-p.abs())), sig(p) - label
+        la, ga = p.clamp_min(0) + (p * label).abs() + torch.log1p(torch.exp(-p.abs())), sig(p) + abs(label)
+    elif mode == 3:
+        l, g = sg * p, torch.full_like(p, sg)
+        la, ga = p.abs(), torch.ones_like(p)
+    elif mode == 4:
+        t = 1 + sg * p
+        l, g = t.clamp_min(0), torch.where(t > 0, torch.full_like(p, sg), torch.zeros_like(p))
+        la, ga = torch.where(t > 0, 1 + p.abs(), torch.zeros_like(p)), g.abs()
+    else:
+        assert mode == 5
+        q = sig(p)
+        l, g = q - q * label + torch.log1p(torch.exp(-q)), (sig(q) - label) * q * (1 - q)
+        la, ga = q + q * abs(label) + torch.log1p(torch.exp(-q)), (sig(q) + abs(label)) * q * (1 + q)
+    k = abs(coeff) / total
+    loss = coeff / total * l.sum()
+    ul = U * (math.sqrt(total) + GAN_L_ROUNDINGS[mode] + 1) * k * la.sum() + workgroups * 2.0 ** -41
+    gk = grad_coeff / total
+    return {"loss": (loss.reshape(1), ul.reshape(1)), "dpred": (gk * g, U * GAN_G_ROUNDINGS[mode] * abs(gk) * ga)}
+
+
+def l1(a, b, coeff, grad0=None, workgroups=1):
+    """vts_l1: "loss" = coeff * sum |a - b| (one rounding per term, K = n addends, 2^-41 per workgroup); "grad" (+)= coeff * sign(a - b):
+    exact without accumulate (unit 0), one rounding with"""
+    a, b = _f64(a).reshape(-1), _f64(b).reshape(-1)
+    coeff = _f32(coeff)
+    d = a - b
+    loss = coeff * d.abs().sum()
+    ul = U * (math.sqrt(d.numel()) + 1) * abs(coeff) * (a.abs() + b.abs()).sum() + workgroups * 2.0 ** -41
+    g = coeff * torch.sign(d)
+    ug = torch.zeros_like(g)
+    if grad0 is not None:
+        o = _f64(grad0).reshape(-1)
+        g, ug = g + o, U * (o.abs() + abs(coeff) * torch.sign(d).abs())
+    return {"loss": (loss.reshape(1), ul.reshape(1)), "grad": (g, ug)}
+
+
+def _clamped(off, size, length):
+    return (int(off) + torch.arange(size)).clamp(0, length - 1)
+
+
+def patch_gather(src, img, offx, offy, size):
+    """vts_patch_gather: out[p, c, y, x] = src[img[p], c, clamp(offy[p] + y, 0, H - 1), clamp(offx[p] + x, 0, W - 1)], in src's own dtype"""
+    h, w = src.shape[-2:]
+    out = [src[int(i)][:, _clamped(oy, size, h)[:, None], _clamped(ox, size, w)[None, :]] for i, ox, oy in zip(img, offx, offy)]
+    return torch.stack(out, 0)
+
+
+def patch_scatter_bwd(dpatch, offx, offy, ppi, n, h, w, dsrc0=None):
+    """vts_patch_scatter_bwd, the adjoint of the gather: dsrc[i, c, Y, X] (+)= sum of dpatch[p, c, y, x] over the patches p of image i
+    (p // ppi = i) and the (y, x) whose clamped source position is (Y, X).  K = addends of the element; K = 0: exactly 0 (or the seed)."""
+    g = _f64(dpatch)
+    P, c, size = g.shape[0], g.shape[1], g.shape[2]
+    assert P == n * ppi
+    ref, a, k = g.new_zeros(n, c, h * w), g.new_zeros(n, c, h * w), g.new_zeros(n, h * w)
+    for p in range(P):
+        idx = (_clamped(offy[p], size, h)[:, None] * w + _clamped(offx[p], size, w)[None, :]).reshape(-1)
+        ref[p // ppi].index_add_(1, idx, g[p].reshape(c, -1))
+        a[p // ppi].index_add_(1, idx, g[p].abs().reshape(c, -1))
+        k[p // ppi].index_add_(0, idx, g.new_ones(idx.numel()))
+    unit = U * torch.sqrt(k).unsqueeze(1) * a
+    if dsrc0 is not None:
+        o = _f64(dsrc0).reshape(n, c, h * w)
+        ref, unit = ref + o, unit + U * (o.abs() + a) * (k > 0).unsqueeze(1)
+    return {"dsrc": (ref.view(n, c, h, w), unit.view(n, c, h, w))}
+
+
+def _bs(x, xa, rb, rs, m, r):
+    """DiffAugment 'bs' times the mask on value x / magnitude xa [N, 3, HW]: ((x1 - mean) k + mean) m, x1 = x + (rb - 0.5), k = 2 rs"""
+    n = x.shape[0]
+    db, k = _f64(rb).view(n, 1, 1) - 0.5, 2 * _f64(rs).view(n, 1, 1)
+    x1, a1 = x + db, xa + _f64(rb).abs().view(n, 1, 1) + 0.5
+    mean, amean = x1.mean(1, keepdim=True), a1.mean(1, keepdim=True)
+    return ((x1 - mean) * k + mean) * m, U * r * ((a1 + amean) * k.abs() + amean) * m.abs()
+
+
+def g_post(g_out, M, scale_nz, rb=None, rs=None, S=None):
+    """vts_g_post / vts_g_post_stack on g_out [N, 5, H, W], M [N, 1, H, W]:
+      fake_I = g[:, :3] M, fake_T = g[:, 3:] M (1 rounding);  fake_N = (tx, ty, nz) / max(|(tx, ty, nz)|, 1e-12), nz = scale_nz (r = 7:
+      the product with M, squares and adds through the root, the root, the division, the product);  aug_fake_I = bs(fake_I; rb, rs) M
+      (r = 10: g M, rb - 0.5, the add, the 3-term mean and its division, subtract, scale, add, mask);  stack_S = S, stack_M = M (copies)."""
+    g, m = _f64(g_out), _f64(M)
+    n, _, h, w = g.shape
+    g, m = g.reshape(n, 5, h * w), m.reshape(n, 1, h * w)
+    nz = _f32(scale_nz)
+    t = g * m
+    out = {"fake_I": (t[:, :3], U * t[:, :3].abs()), "fake_T": (t[:, 3:], U * t[:, 3:].abs())}
+    v = torch.cat([t[:, 3:], torch.full_like(t[:, :1], nz)], 1)
+    nv = v / v.norm(dim=1, keepdim=True).clamp_min(1e-12)
+    out["fake_N"] = (nv, 7 * U * nv.abs())
+    if rb is not None:
+        out["aug_fake_I"] = _bs(t[:, :3], t[:, :3].abs(), rb, rs, m, 10)
+    out["stack_M"] = (m, torch.zeros_like(m))
+    if S is not None:
+        s = _f64(S).reshape(n, 1, h * w)
+        out["stack_S"] = (s, torch.zeros_like(s))
+    return out
+
+
+def diffaug_bs_mask(x, M, rb, rs):
+    """vts_diffaug_bs_mask: aug = bs(x; rb, rs) M on x [N, 3, H, W] (M None: no mask); r = 9"""
+    x = _f64(x)
+    n = x.shape[0]
+    x = x.reshape(n, 3, -1)
+    m = _f64(M).reshape(n, 1, -1) if M is not None else torch.ones_like(x[:, :1])
+    return {"aug": _bs(x, x.abs(), rb, rs, m, 9)}
+
+
+def diffaug_op(x, op, pf=None, pi0=None, pi1=None, noise=None, M=None):
+    """vts_diffaug_op, one letter of b s c t o n on x [N, C, H, W], times M when given (one more rounding); see include/vts.h.
+      b r = 2; s r = C + 3 (the channel mean: C - 1 adds and a division; subtract, scale, add); c r = 4 (pf + 0.5, subtract, scale, add)
+      plus the mean over K = C H W elements, u (sqrt(K) + 1) mean|x|, through |k| + 1; t, o: copies and exact zeros; n r = 2"""
+    x = _f64(x)
+    n, c, h, w = x.shape
+    m = _f64(M).view(n, 1, h, w) if M is not None else torch.ones_like(x[:, :1])
+    rm = 1 if M is not None else 0
+    col = lambda t: _f64(t).view(n, 1, 1, 1)
+    xa = x.abs()
+    if op == "b":
+        ref, a, r = x + (col(pf) - 0.5), xa + col(pf).abs() + 0.5, 2
+    elif op == "s":
+        mean, amean, k = x.mean(1, keepdim=True), xa.mean(1, keepdim=True), 2 * col(pf)
+        ref, a, r = (x - mean) * k + mean, (xa + amean) * k.abs() + amean, c + 3
+    elif op == "c":
+        mean, amean = x.mean((1, 2, 3), keepdim=True), xa.mean((1, 2, 3), keepdim=True)
+        k, ka = col(pf) + 0.5, col(pf).abs() + 0.5
+        ref, a, r = (x - mean) * k + mean, (xa + amean) * ka + amean, 4
+        extra = U * (math.sqrt(c * h * w) + 1) * amean * (ka + 1)
+        return {"out": (ref * m, (U * (r + rm) * a + extra) * m.abs())}
+    elif op == "t":
+        ref = torch.zeros_like(x)
+        for i in range(n):
+            ref[i] = _window(x[i], int(pi0[i]), int(pi1[i]), h, w)
+        a, r = ref.abs(), 0
+    elif op == "o":
+        ch, cw = int(h * 0.5 + 0.5), int(w * 0.5 + 0.5)
+        keep = torch.ones_like(x[:, :1])
+        for i in range(n):
+            r0, c0 = int(pi0[i]) - ch // 2, int(pi1[i]) - cw // 2
+            rows = sorted(set(min(max(r0 + j, 0), h - 1) for j in range(ch)))
+            cols = sorted(set(min(max(c0 + j, 0), w - 1) for j in range(cw)))
+            keep[i, 0, rows[0]:rows[-1] + 1, cols[0]:cols[-1] + 1] = 0
+        ref, a, r = x * keep, xa * keep, 0
+    else:
+        assert op == "n"
+        z = _f64(noise)
+        ref, a, r = x + col(pf) * z, xa + (col(pf) * z).abs(), 2
+    return {"out": (ref * m, U * (r + rm) * a * m.abs())}
+
+
+def g_out_grad(d_fake_I, d_fake_T, M, g_out, coarse=None):
+    """vts_g_out_grad / vts_g_out_grad_pool: d_raw = cat(d_fake_I [+ pool adjoint of `coarse`], d_fake_T) M (1 - g_out^2); a NULL
+    gradient is zero.  r = 4 (square, 1 - ., two products) on |up| |M| (1 + g^2); the pooled form adds the adjoint's unit and one add."""
+    g, m = _f64(g_out), _f64(M)
+    n, _, h, w = g.shape
+    up, au, uu = g.new_zeros(n, 5, h, w), g.new_zeros(n, 5, h, w), g.new_zeros(n, 5, h, w)
+    if d_fake_I is not None:
+        up[:, :3], au[:, :3] = _f64(d_fake_I), _f64(d_fake_I).abs()
+    if coarse is not None:
+        adj, uadj = avgpool3s2_bwd(coarse, h, w)["dx"]
+        aadj = _pool_adjoint(_f64(coarse).abs(), h, w)
+        uu[:, :3] = uadj + U * (au[:, :3] + aadj)
+        up[:, :3], au[:, :3] = up[:, :3] + adj, au[:, :3] + aadj
+    if d_fake_T is not None:
+        up[:, 3:], au[:, 3:] = _f64(d_fake_T), _f64(d_fake_T).abs()
+    f, fa = m * (1 - g * g), m.abs() * (1 + g * g)
+    return {"d_raw": (up * f, 4 * U * au * fa + uu * fa)}
+
+
+def mask_mul(x, M):
+    """vts_mask_mul: y = x M, one rounding"""
+    y = _f64(x) * _f64(M)
+    return {"y": (y, U * y.abs())}
+
+
+def spe_grid(n, h, w, dim):
+    """vts_spe_grid: out[n, d, y, x], e = d % dim, i = e % (dim / 2), pos = (d < dim ? x : y) + 1, a = pos exp(-i ln(1e4) / (dim / 2 - 1)),
+    out = e < dim / 2 ? sin(a) : cos(a).  The unit carries the ARGUMENT: ln (2 roundings), division, the product with i and the
+    exponential's own 2 act on t = i ln(1e4) / (half - 1) as a relative error 4 |t| + 2 of the frequency, the product with pos adds 1:
+    unit = u (2 |out| + |a| (4 |t| + 3)), t = 0 (frequency exactly 1, a an exact integer): u 2 |out|."""
+    half = dim // 2
+    i = torch.arange(half, dtype=torch.float64)
+    t = i * (math.log(10000.0) / (half - 1))
+    f = torch.exp(-t)
+
+    def axis(length):
+        a = torch.arange(1, length + 1, dtype=torch.float64).view(1, -1) * f.view(-1, 1)          # [half, L]
+        ua = a * (4 * t.view(-1, 1) + 3) * (t.view(-1, 1) > 0)
+        v = torch.cat([torch.sin(a), torch.cos(a)], 0)
+        return v, U * (2 * v.abs() + torch.cat([ua, ua], 0))
+    xv, xu = axis(w)
+    yv, yu = axis(h)
+    ref = torch.cat([xv[:, None, :].expand(dim, h, w), yv[:, :, None].expand(dim, h, w)], 0)
+    unit = torch.cat([xu[:, None, :].expand(dim, h, w), yu[:, :, None].expand(dim, h, w)], 0)
+    return {"out": (ref[None].expand(n, 2 * dim, h, w).contiguous(), unit[None].expand(n, 2 * dim, h, w).contiguous())}
+
+
+def adam_flat(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0):
+    """vts_adam_flat / vts_adam_flat_dev, torch.optim.Adam's defaults on gr = g grad_scale:
+      m' = beta1 m + (1 - beta1) gr (r = 4),  v' = beta2 v + (1 - beta2) gr^2 (r = 6),
+      p' = p - (lr / bc1) m' / (sqrt(v') / sqrt(bc2) + eps),  bc = 1 - beta^step.
+    The units of m' and v' are propagated into p'; a bias correction is a power (2 roundings) and a subtraction on absref 1 + beta^step
+    (near step 1 that is the cancellation an fp32 evaluation of 1 - beta^step has), the root, the quotient, + eps, the division, the
+    product with the step size and the final subtraction one rounding each.  m' = 0 exactly (g = m = 0): p' = p exactly, unit 0."""
+    p, g, m, v = _f64(p), _f64(g), _f64(m), _f64(v)
+    lr, b1, b2, eps, gs = _f32(lr), _f32(beta1), _f32(beta2), _f32(eps), _f32(grad_scale)
+    gr = g * gs
+    m1, ma = b1 * m + (1 - b1) * gr, (b1 * m).abs() + ((1 - b1) * gr).abs()
+    v1 = b2 * v + (1 - b2) * gr * gr
+    um, uv = 4 * U * ma, 6 * U * v1
+    bc1, bc2 = 1 - b1 ** step, 1 - b2 ** step
+    rel1, rel2 = 3 * U * (1 + b1 ** step) / bc1, 3 * U * (1 + b2 ** step) / bc2
+    ss = lr / bc1
+    root = torch.sqrt(v1) / math.sqrt(bc2)
+    denom = root + eps
+    uden = root * (0.5 * 6 * U + 0.5 * rel2 + 3 * U) + U * denom
+    upd, upda = ss * m1 / denom, abs(ss) * ma / denom
+    uupd = abs(ss) * um / denom + upda * (uden / denom + rel1 + 3 * U)
+    up = torch.where(ma > 0, uupd + U * (p.abs() + upda), torch.zeros_like(p))
+    return {"p": (p - upd, up), "m": (m1, um), "v": (v1, uv)}
+
+
+# ---- exact judges: data movement, byte staging, the sampler --------------------------------------------------------------------------------
+
+def patch_jobs(jobs, size):
+    """vts_patch_jobs: every job {dst_c0, C, P, and src (+ img, offx, offy: gather; without: copy of src [P, C, size, size]) or fill} as
+    (dst_c0, block [P, C, size, size] float32)"""
+    out = []
+    for q in jobs:
+        if q.get("src") is None:
+            blk = torch.full((q["P"], q["C"], size, size), q["fill"], dtype=torch.float32)
+        elif q.get("img") is None:
+            blk = q["src"][:q["P"], :q["C"]].clone()
+        else:
+            blk = patch_gather(q["src"][:, :q["C"]], q["img"], q["offx"], q["offy"], size)
+        out.append((q["dst_c0"], blk))
+    return out
+
+
+def pool_query(images, store, ret_slot, put_slot):
+    """vts_pool_query: for n in order: out[n] = ret_slot[n] < 0 ? images[n] : store[ret_slot[n]], then store[put_slot[n]] = images[n]
+    (put_slot[n] >= 0); returns (out, the store afterwards)"""
+    store, out = store.clone(), torch.empty_like(images)
+    for n in range(images.shape[0]):
+        r, w = int(ret_slot[n]), int(put_slot[n])
+        out[n] = images[n] if r < 0 else store[r]
+        if w >= 0:
+            store[w] = images[n]
+    return out, store
+
+
+def u8_expand(src, normalize):
+    """vts_u8_expand: ToTensor [+ Normalize(0.5, 0.5)] in IEEE fp32: b / 255 [then (t - 0.5) / 0.5], correctly rounded each"""
+    t = src.to(torch.float32) / torch.tensor(255.0)
+    return (t - 0.5) / 0.5 if normalize else t
+
+
+def input_images_u8(S, I, M):
+    """vts_input_images_u8: (M_out, S_out, I_out) = (M / 255, expand(S) M_out, expand(I) M_out) in IEEE fp32 (M None: mask 1; I None: None)"""
+    m = u8_expand(M, False) if M is not None else torch.ones(S.shape, dtype=torch.float32)
+    return (m if M is not None else None), u8_expand(S, True) * m, (u8_expand(I, True) * m if I is not None else None)
+
+
+def mask_candidates(M):
+    """vts_mask_candidates: cand[n, y, x] = any(M[n, y - 1 .. y + 15, x - 1 .. x + 15] > 0) on the (H - 14) x (W - 14) grid (uint8) and
+    prefix [n, H - 14 + 1] (int32): prefix[n, y] = candidates in the rows before y"""
+    n, _, h, w = M.shape
+    b = torch.nn.functional.pad((M > 0).to(torch.float64), (1, 1, 1, 1))
+    cand = torch.nn.functional.max_pool2d(b, 17, 1).view(n, h - 14, w - 14).to(torch.uint8)
+    prefix = torch.zeros(n, h - 14 + 1, dtype=torch.int32)
+    prefix[:, 1:] = cand.sum(2, dtype=torch.int64).cumsum(1).to(torch.int32)
+    return cand, prefix
+
+
+def mask_select(cand, ranks):
+    """vts_mask_select: (offx, offy) [N * K] int32 of the candidate with row-major rank ranks[n, k]"""
+    n, k = ranks.shape
+    offx, offy = torch.empty(n, k, dtype=torch.int32), torch.empty(n, k, dtype=torch.int32)
+    for i in range(n):
+        pos = torch.nonzero(cand[i])
+        offy[i], offx[i] = pos[ranks[i], 0].to(torch.int32), pos[ranks[i], 1].to(torch.int32)
+    return offx.reshape(-1), offy.reshape(-1)
+
+
+_M64 = (1 << 64) - 1
+
+
+def splitmix64(x):
+    x = (x + 0x9E3779B97F4A7C15) & _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def mask_sample_ranks(counts, K, seed):
+    """vts_mask_sample_ranks in Python integers: per image n with c candidates, Floyd's algorithm over j = c - K .. c - 1 with
+    t = mulhi64(splitmix64(splitmix64(seed ^ n 0xD1B54A32D192ED03) + i), j + 1) for draw i, inserting t, or j if t is already drawn;
+    c < K: ranks wrap (q % c, or 0 for an empty image).  int64 [N, K]"""
+    out = torch.empty(len(counts), K, dtype=torch.int64)
+    for n, c in enumerate(int(v) for v in counts):
+        if c < K:
+            out[n] = torch.tensor([q % c if c > 0 else 0 for q in range(K)])
+            continue
+        base = splitmix64((seed & _M64) ^ ((n * 0xD1B54A32D192ED03) & _M64))
+        seen, order = set(), []
+        for i in range(K):
+            j = c - K + i
+            t = (splitmix64((base + i) & _M64) * (j + 1)) >> 64
+            pick = j if t in seen else t
+            seen.add(pick)
+            order.append(pick)
+        out[n] = torch.tensor(order)
+    return out
 
 
 def worst(got, ref, unit):

@@ -21,7 +21,7 @@ import torch.nn.functional as F
 # ----------------------------------------------------------------------------
 
 
-def spe_grid(n, h, w, dim=4, device="cpu"):
+def spe_grid(n, h, w, dim=4, device="cpu", dtype=torch.float):
     """SinusoidalPositionalEmbedding(dim, padding_idx=0)(x) for a 4-D x.
 
     thirdparty/mmgeneration/positional_encoding.py:54-82 (get_embedding),
@@ -29,10 +29,10 @@ def spe_grid(n, h, w, dim=4, device="cpu"):
     f_i = exp(-i ln(1e4)/(dim/2-1)); grid = cat(x-embedding over rows, y-embedding over cols).
     """
     half = dim // 2
-    f = torch.exp(torch.arange(half, dtype=torch.float) * -(np.log(10000) / (half - 1)))
+    f = torch.exp(torch.arange(half, dtype=dtype) * -(np.log(10000) / (half - 1)))
 
     def axis(length):
-        pos = torch.arange(length + 1, dtype=torch.float).unsqueeze(1) * f.unsqueeze(0)
+        pos = torch.arange(length + 1, dtype=dtype).unsqueeze(1) * f.unsqueeze(0)
         emb = torch.cat([torch.sin(pos), torch.cos(pos)], dim=1)  # [L+1, dim]
         return emb[1:].t()  # [dim, L]; row 0 is the padding row
 

@@ -577,7 +577,7 @@ def test_channel_sum_and_act_bwd(fuse_finalize):
 
 @pytest.mark.parametrize("hw", [(64, 64), (33, 47), (2, 2), (513, 17), (66, 130), (33, 46), (5, 4), (131, 258)])
 def test_avgpool(hw):
-    from vts import ops
+    from vts import lib as L, ops
 
     dev = _dev()
     x = detrand.uniform((2, 4, hw[0], hw[1]), 10, "x").requires_grad_(True)
@@ -585,6 +585,9 @@ def test_avgpool(hw):
     cot = detrand.uniform(tuple(y.shape), 10, "c")
     (y * cot).sum().backward()
     yk = ops.avgpool(x.detach().to(dev))
+    # even-width planes of at least 4 columns take the rows-of-four instance (a fresh tensor is 8-byte aligned with an even batch stride)
+    rows4 = hw[1] % 2 == 0 and hw[1] >= 4
+    assert L.load().vts_last_kernel().decode() == ("avgpool_rows4_kernel" if rows4 else "avgpool_kernel")
     assert rel(yk, y) < 1e-6
     dx = torch.ones(2, 4, hw[0], hw[1], device=dev)
     ops.avgpool_bwd(cot.to(dev), dx, accumulate=True)
@@ -609,7 +612,7 @@ def test_ganloss(mode, real):
 
 
 def test_l1_and_adam():
-    from vts import ops
+    from vts import lib as L, ops
 
     dev = _dev()
     a = detrand.uniform((2, 3, 17, 19), 12, "a").requires_grad_(True)
@@ -619,6 +622,7 @@ def test_l1_and_adam():
     slot = ops.loss_slots(1, dev)
     g = torch.empty(2, 3, 17, 19, device=dev)
     ops.l1(a.detach().to(dev), b.to(dev), 100.0 / a.numel(), slot, g)
+    assert L.load().vts_last_kernel().decode() == "l1_kernel vec=0"      # n = 1938 is no multiple of 4; the vec instance: tests/test_step_glue_gpu.py
     assert abs(ops.loss_values(slot)[0] - ref.item()) < 1e-4 * abs(ref.item())
     assert rel(g, a.grad) < 1e-6
     # Adam, 3 steps, beta1 = 0 like the reference

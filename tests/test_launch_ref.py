@@ -362,3 +362,226 @@ def test_wide_judges_catch_one_dropped_product():
         assert at == (1 * 3 + y) * 4 + x
         smallest.append(ratio)
     assert min(smallest) > 8.0, smallest
+
+
+# ---- the glue judges (loss, optimiser, pyramid, patches, post-processing, augmentation, sampler) against torch / oracle.nets in float64 ----
+from oracle import nets  # noqa: E402
+
+TOL = 1e-12
+
+
+def close(a, b):
+    return float((a.reshape(-1) - b.reshape(-1)).abs().max()) <= TOL * max(1.0, float(b.abs().max()))
+
+
+def flagged(ref, unit):
+    """a single element (the one with the largest unit) changed by 16 units is what worst() reports, at that element"""
+    ref, unit = ref.reshape(-1), unit.reshape(-1)
+    i = int(torch.argmax(unit))
+    assert float(unit[i]) > 0
+    got = ref.clone()
+    got[i] += 16 * unit[i]
+    ratio, at = R.worst(got, ref, unit)
+    assert at == i and 15.9 < ratio < 16.1, (at, i, ratio)
+    assert R.worst(ref.clone(), ref, unit)[0] == 0
+
+
+@pytest.mark.parametrize("hw", [(1, 1), (1, 4), (2, 2), (5, 7), (17, 130), (66, 65)])
+def test_avgpool_judges_match_avg_pool2d_and_its_autograd(hw):
+    g = torch.Generator().manual_seed(hw[0] * 131 + hw[1])
+    x = rnd(g, 2, 3, *hw).requires_grad_(True)
+    y = F.avg_pool2d(x, 3, 2, 1, count_include_pad=False)
+    cot, dx0 = rnd(g, *y.shape), rnd(g, 2, 3, *hw)
+    (y * cot).sum().backward()
+    ref, unit = R.avgpool3s2(x)["y"]
+    assert close(ref, y.detach()) and (unit >= 0).all()
+    assert close(R.avgpool3s2_bwd(cot, *hw)["dx"][0], x.grad)
+    assert close(R.avgpool3s2_bwd(cot, *hw, dx0=dx0)["dx"][0], x.grad + dx0)
+    flagged(ref, unit)
+    flagged(*R.avgpool3s2_bwd(cot, *hw, dx0=dx0)["dx"])
+
+
+GAN_NAMES = {0: "nonsaturating", 1: "lsgan", 2: "vanilla", 3: "wgan", 4: "hinge"}
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2, 3, 4, 5])
+@pytest.mark.parametrize("real", [True, False])
+def test_ganloss_judge_matches_gan_loss_single_in_float64(mode, real):
+    g = torch.Generator().manual_seed(mode * 2 + real)
+    p = (rnd(g, 3, 1, 9, 11) * 12).requires_grad_(True)          # beyond +-20: the softplus threshold
+    label, coeff, gcoeff = (0.75 if real else 0.125), 2.5, -0.75          # exact in fp32
+    if mode == 5:
+        loss = F.binary_cross_entropy_with_logits(torch.sigmoid(p), torch.full_like(p, label))
+    else:
+        loss = nets.gan_loss_single(p, real, GAN_NAMES[mode], label, label).mean()
+    loss.backward()
+    out = R.ganloss(p, mode, real, label, coeff, gcoeff, workgroups=2)
+    assert close(out["loss"][0], coeff * loss.detach())
+    assert close(out["dpred"][0], gcoeff * p.grad)
+    assert float(out["loss"][1]) >= 2 * 2.0 ** -41
+    flagged(*out["dpred"])
+    flagged(*out["loss"])
+
+
+def test_l1_judge_matches_l1_loss_and_its_autograd():
+    g = torch.Generator().manual_seed(5)
+    a, b, g0 = rnd(g, 2, 3, 17, 19).requires_grad_(True), rnd(g, 2, 3, 17, 19), rnd(g, 2 * 3 * 17 * 19)
+    b.view(-1)[:40] = a.detach().view(-1)[:40]                    # a stretch of exact ties: sign 0
+    coeff = 0.5
+    loss = F.l1_loss(a, b, reduction="sum") * coeff
+    loss.backward()
+    out = R.l1(a, b, coeff)
+    assert close(out["loss"][0], loss.detach()) and close(out["grad"][0], a.grad)
+    assert (out["grad"][1] == 0).all() and (out["grad"][0][:40] == 0).all()
+    acc = R.l1(a, b, coeff, grad0=g0)
+    assert close(acc["grad"][0], a.grad.reshape(-1) + g0)
+    flagged(*out["loss"])
+    flagged(*acc["grad"])
+
+
+def test_patch_judges_match_gather_patches_and_its_autograd():
+    g = torch.Generator().manual_seed(6)
+    n, c, h, w, ppi, size = 2, 2, 33, 31, 5, 8
+    src = rnd(g, n, c, h, w).requires_grad_(True)
+    offx = torch.tensor([0, -5, 28, 40, 0, 3, 3, -20, 30, 12])
+    offy = torch.tensor([0, 30, -3, 2, 0, 50, 50, 4, 31, 9])
+    img = torch.arange(n).repeat_interleave(ppi)
+    ref = torch.cat([nets.gather_patches(src[i:i + 1], offx[i * ppi:(i + 1) * ppi], offy[i * ppi:(i + 1) * ppi], size) for i in range(n)], 0)
+    cot, seed = rnd(g, *ref.shape), rnd(g, n, c, h, w)
+    (ref * cot).sum().backward()
+    assert torch.equal(R.patch_gather(src.detach(), img, offx, offy, size), ref.detach())
+    out = R.patch_scatter_bwd(cot, offx, offy, ppi, n, h, w)["dsrc"]
+    assert close(out[0], src.grad) and ((out[1] == 0) == (src.grad == 0)).all()
+    acc = R.patch_scatter_bwd(cot, offx, offy, ppi, n, h, w, dsrc0=seed)["dsrc"]
+    assert close(acc[0], src.grad + seed) and (acc[1][src.grad == 0] == 0).all()
+    flagged(*acc)
+
+
+def test_g_post_and_diffaug_judges_match_the_oracle_nets():
+    g = torch.Generator().manual_seed(7)
+    n, h, w = 2, 9, 7
+    go, S = torch.tanh(rnd(g, n, 5, h, w)), rnd(g, n, 1, h, w)
+    M = (rnd(g, n, 1, h, w) > 0).to(D64)
+    rb, rs = torch.rand(n, generator=g, dtype=D64), torch.rand(n, generator=g, dtype=D64)
+    out = R.g_post(go, M, 0.25, rb, rs, S)
+    fI, fT = go[:, :3] * M, go[:, 3:] * M
+    assert close(out["fake_I"][0], fI) and close(out["fake_T"][0], fT)
+    assert close(out["fake_N"][0], nets.compute_normal(fT, 0.25))
+    assert close(out["aug_fake_I"][0], nets.diffaug_bs(fI, rb, rs) * M)
+    assert torch.equal(out["stack_S"][0].reshape(-1), S.reshape(-1)) and torch.equal(out["stack_M"][0].reshape(-1), M.reshape(-1))
+    zero = R.g_post(go, torch.zeros_like(M), 0.0)["fake_N"]
+    assert (zero[0] == 0).all() and (zero[1] == 0).all()          # the 1e-12 clamp: 0 / 1e-12
+    x = rnd(g, n, 3, h, w)
+    assert close(R.diffaug_bs_mask(x, M, rb, rs)["aug"][0], nets.diffaug_bs(x, rb, rs) * M)
+    assert close(R.diffaug_bs_mask(x, None, rb, rs)["aug"][0], nets.diffaug_bs(x, rb, rs))
+    for k in ("fake_I", "fake_N", "aug_fake_I"):
+        flagged(*out[k])
+    flagged(*R.diffaug_bs_mask(x, M, rb, rs)["aug"])
+
+
+@pytest.mark.parametrize("letter", list("bscton"))
+@pytest.mark.parametrize("masked", [False, True])
+def test_diffaug_op_judge_matches_the_oracle_diffaug(letter, masked):
+    g = torch.Generator().manual_seed(ord(letter))
+    n, c, h, w = 2, 3, 9, 7
+    x = rnd(g, n, c, h, w) + 3.0
+    M = (rnd(g, n, 1, h, w) > 0).to(D64) if masked else None
+    d = {"r": torch.rand(n, generator=g, dtype=D64), "tx": torch.tensor([-2, 9]), "ty": torch.tensor([1, -1]),
+         "ox": torch.tensor([0, 9]), "oy": torch.tensor([3, 7]), "sigma": torch.tensor([0.05, 0.0], dtype=D64), "noise": rnd(g, n, c, h, w)}
+    want = nets.diffaug(x, letter, [d])
+    want = want * M if masked else want
+    pf = d["sigma"] if letter == "n" else d["r"]
+    pi = (d["tx"], d["ty"]) if letter == "t" else (d["ox"], d["oy"])
+    ref, unit = R.diffaug_op(x, letter, pf=pf, pi0=pi[0], pi1=pi[1], noise=d["noise"], M=M)["out"]
+    assert close(ref, want)
+    if letter in "to" and not masked:
+        assert (unit == 0).all()
+    else:
+        flagged(ref, unit)
+
+
+def test_g_out_grad_judge_matches_autograd_of_the_masked_tanh_outputs():
+    g = torch.Generator().manual_seed(8)
+    n, h, w = 2, 5, 4
+    raw = rnd(g, n, 5, h, w).requires_grad_(True)
+    M = (rnd(g, n, 1, h, w) > 0).to(D64)
+    dI, dT, dc = rnd(g, n, 3, h, w), rnd(g, n, 2, h, w), rnd(g, n, 3, 3, 2)
+    go = torch.tanh(raw)
+    fI, fT = go[:, :3] * M, go[:, 3:] * M
+    ((fI * dI).sum() + (fT * dT).sum() + (F.avg_pool2d(fI, 3, 2, 1, count_include_pad=False) * dc).sum()).backward()
+    out = R.g_out_grad(dI, dT, M, go.detach(), coarse=dc)["d_raw"]
+    assert close(out[0], raw.grad)
+    plain = R.g_out_grad(None, dT, M, go.detach())["d_raw"]
+    assert (plain[0][:, :3] == 0).all() and (plain[1][:, :3] == 0).all()
+    flagged(*out)
+    flagged(*R.g_out_grad(dI, dT, M, go.detach())["d_raw"])
+    flagged(*R.mask_mul(dI, M)["y"])
+    assert close(R.mask_mul(dI, M)["y"][0], dI * M)
+
+
+@pytest.mark.parametrize("dim", [4, 8])
+def test_spe_judge_matches_the_oracle_grid_and_carries_the_argument(dim):
+    ref, unit = R.spe_grid(2, 3, 1100, dim)["out"]
+    assert close(ref, nets.spe_grid(2, 3, 1100, dim, dtype=D64))
+    # a few u of relative error in the frequency move sin(pos f) by |pos f| times that: the unit must grow with the position
+    assert float(unit[0, 1, 0, 1099]) > 100 * float(unit[0, 1, 0, 0])
+    assert float(unit[0, 0, 0, 1099]) <= 2 * R.U           # frequency exactly 1: only the sine's own rounding
+    flagged(ref, unit)
+
+
+@pytest.mark.parametrize("betas", [(0.0, 0.99), (0.5, 0.999)])
+def test_adam_judge_matches_adam_update_and_torch_optim_adam(betas):
+    g = torch.Generator().manual_seed(9)
+    n, lr, eps = 50, 1e-3, 1e-8
+    lr32, eps32, b1, b2 = R._f32(lr), R._f32(eps), R._f32(betas[0]), R._f32(betas[1])
+    p0 = rnd(g, n)
+    grads = [rnd(g, n) * 10.0 ** (-2 * s) for s in range(3)]
+    grads[0][:5] = 0
+    param = p0.clone().requires_grad_(True)
+    opt = torch.optim.Adam([param], lr=lr32, betas=(b1, b2), eps=eps32)
+    p, m, v = p0.clone(), torch.zeros(n, dtype=D64), torch.zeros(n, dtype=D64)
+    pn, mn, vn = p0.clone(), torch.zeros(n, dtype=D64), torch.zeros(n, dtype=D64)
+    for step, gr in enumerate(grads, 1):
+        param.grad = gr.clone()
+        opt.step()
+        nets.adam_update(pn, gr, mn, vn, step, lr32, b1, b2, eps32)
+        out = R.adam_flat(p, gr * 8, m, v, lr, betas[0], betas[1], eps, step, grad_scale=0.125)
+        if step == 1:
+            assert (out["p"][1][:5] == 0).all() and torch.equal(out["p"][0][:5], p[:5])      # g = m = v = 0: no update, exactly
+            assert (out["p"][1][5:] > 0).all()
+        p, m, v = out["p"][0], out["m"][0], out["v"][0]
+        assert close(p, param.detach()) and close(p, pn) and close(m, mn) and close(v, vn)
+    for k in ("p", "m", "v"):
+        flagged(*out[k])
+
+
+def test_sampler_and_staging_judges():
+    g = torch.Generator().manual_seed(10)
+    M = torch.zeros(2, 1, 46, 47, dtype=D64)
+    M[0, 0, 20:23, 5:9], M[0, 0, 45, 46], M[1, 0, 0, 0] = 1.0, 0.5, 2.0
+    cand, prefix = R.mask_candidates(M)
+    for i in range(2):
+        pos = nets.dilated_mask_positions(M[i:i + 1])
+        want = torch.zeros(32, 33, dtype=torch.uint8)
+        want[pos[:, 0], pos[:, 1]] = 1
+        assert torch.equal(cand[i], want) and int(prefix[i, -1]) == pos.shape[0] and int(prefix[i, 0]) == 0
+        ranks = torch.tensor([[0, pos.shape[0] - 1, pos.shape[0] // 2]])
+        ox, oy = R.mask_select(cand[i:i + 1], ranks)
+        assert torch.equal(oy.long(), pos[ranks[0], 0]) and torch.equal(ox.long(), pos[ranks[0], 1])
+    assert (prefix[:, 1:] >= prefix[:, :-1]).all()
+    counts = [1000, 70, 3, 0]
+    r = R.mask_sample_ranks(counts, 65, 12345)
+    assert r.shape == (4, 65) and len(set(r[0].tolist())) == 65 and 0 <= int(r[0].min()) and int(r[0].max()) < 1000
+    assert sorted(r[1].tolist()) == sorted(set(r[1].tolist())) and int(r[1].max()) < 70
+    assert r[2].tolist() == [q % 3 for q in range(65)] and r[3].tolist() == [0] * 65
+    assert not torch.equal(r[0], R.mask_sample_ranks(counts, 65, 12346)[0])
+    assert R.splitmix64(0) == 0xE220A8397B1DCDAF                 # the published first output of splitmix64 seeded with 0
+    # byte staging: IEEE fp32 division / subtraction, every byte value
+    b = torch.arange(256, dtype=torch.uint8)
+    assert torch.equal(R.u8_expand(b, False), b.float() / 255.0) and torch.equal(R.u8_expand(b, True), (b.float() / 255.0 - 0.5) / 0.5)
+    m, s, i3 = R.input_images_u8(b.view(1, 1, 256), b.view(1, 1, 256).expand(1, 3, 256), b.flip(0).view(1, 1, 256))
+    assert torch.equal(s, R.u8_expand(b, True).view(1, 1, 256) * m) and torch.equal(i3[0, 2], s[0, 0])
+    # image pool: a later image draws the slot an earlier one has just filled
+    imgs, store = rnd(g, 3, 4).float(), rnd(g, 2, 4).float()
+    out, st = R.pool_query(imgs, store, torch.tensor([-1, 1, 1]), torch.tensor([1, 1, -1]))
+    assert torch.equal(out[0], imgs[0]) and torch.equal(out[1], imgs[0]) and torch.equal(out[2], imgs[1]) and torch.equal(st[1], imgs[1])

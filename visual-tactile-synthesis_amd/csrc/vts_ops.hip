@@ -753,12 +753,14 @@ inline unsigned blocks_for(int64_t n, int cap = 2048) {
 extern "C" int vts_avgpool3s2(const float* x, int64_t xns, int N, int C, int H, int W, float* y, void* stream) {
   VTS_CHECK_ARG(x && y && N * C <= 65535, "vts_avgpool3s2: bad args");
   const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
-  if (W % 2 == 0 && W >= 4 && (reinterpret_cast<uintptr_t>(x) & 7) == 0 && xns % 2 == 0 && ((int64_t)H * W) % 2 == 0)
+  const bool rows4 = W % 2 == 0 && W >= 4 && (reinterpret_cast<uintptr_t>(x) & 7) == 0 && xns % 2 == 0 && ((int64_t)H * W) % 2 == 0;
+  if (rows4)
     hipLaunchKernelGGL(avgpool_rows4_kernel, dim3(cdiv(OW, 64), cdiv(OH, 16), N * C), dim3(256), 0, (hipStream_t)stream, x, xns, C, H, W,
                        OH, OW, y);
   else
     hipLaunchKernelGGL(avgpool_kernel, dim3(cdiv(OW, 64), cdiv(OH, 4), N * C), dim3(256), 0, (hipStream_t)stream, x, xns, C, H, W, OH,
                        OW, y);
+  vts_set_kernel(rows4 ? "avgpool_rows4_kernel" : "avgpool_kernel");
   VTS_CHECK_LAUNCH("vts_avgpool3s2");
   return VTS_OK;
 }
@@ -768,6 +770,7 @@ extern "C" int vts_avgpool3s2_bwd(const float* dy, int N, int C, int H, int W, f
   const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
   hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(cdiv(W, 64), cdiv(H, 4), N * C), dim3(256), 0, (hipStream_t)stream, dy, C, H, W, OH, OW,
                      dx, dxns, accumulate);
+  vts_set_kernel("avgpool_bwd_kernel");
   VTS_CHECK_LAUNCH("vts_avgpool3s2_bwd");
   return VTS_OK;
 }
@@ -778,6 +781,7 @@ extern "C" int vts_ganloss(const float* pred, int N, int M, int mode, int target
   const int64_t total = (int64_t)N * M;
   hipLaunchKernelGGL(ganloss_kernel, dim3(blocks_for(total, 256)), dim3(256), 0, (hipStream_t)stream, pred, total, mode, target_is_real,
                      target_label, 1.f / (float)total, coeff, grad_coeff, reinterpret_cast<long long*>(loss_out), dpred);
+  vts_set_kernel("ganloss_kernel");
   VTS_CHECK_LAUNCH("vts_ganloss");
   return VTS_OK;
 }
@@ -788,6 +792,7 @@ extern "C" int vts_l1(const float* a, const float* b, int64_t n, float coeff, in
   const int vec = (n % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(grad)) & 15) == 0) ? 1 : 0;
   hipLaunchKernelGGL(l1_kernel, dim3(blocks_for(vec ? n / 4 : n, 1024)), dim3(256), 0, (hipStream_t)stream, a, b, n, coeff,
                      reinterpret_cast<long long*>(loss_out), grad, accumulate, vec);
+  vts_set_kernel(vec ? "l1_kernel vec=1" : "l1_kernel vec=0");
   VTS_CHECK_LAUNCH("vts_l1");
   return VTS_OK;
 }
@@ -797,6 +802,7 @@ extern "C" int vts_patch_gather(const float* src, int64_t sns, int C, int H, int
   VTS_CHECK_ARG(src && img && offx && offy && out && P >= 1 && C >= 1, "vts_patch_gather: bad args");
   hipLaunchKernelGGL(patch_gather_kernel, dim3(P, C), dim3(256), 0, (hipStream_t)stream, src, sns, C, H, W, img, offx, offy, size, out,
                      out_C, out_c0);
+  vts_set_kernel("patch_gather_kernel");
   VTS_CHECK_LAUNCH("vts_patch_gather");
   return VTS_OK;
 }
@@ -812,6 +818,7 @@ __global__ void step_begin_kernel(long long* slots, int nslots, int* counters, i
 extern "C" int vts_step_begin(int64_t* slots, int nslots, int* counters, int ncounters, void* stream) {
   VTS_CHECK_ARG(nslots >= 0 && ncounters >= 0 && nslots <= 256 && ncounters <= 256 && (slots || !nslots) && (counters || !ncounters), "vts_step_begin: bad args");
   hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<long long*>(slots), nslots, counters, ncounters);
+  vts_set_kernel("step_begin_kernel");
   VTS_CHECK_LAUNCH("vts_step_begin");
   return VTS_OK;
 }
@@ -831,6 +838,7 @@ extern "C" int vts_patch_jobs(const vts_patch_job* jobs, int njobs, int size, vo
   }
   t.ch_start[njobs] = ch;
   hipLaunchKernelGGL(patch_jobs_kernel, dim3(pmax, ch), dim3(256), 0, (hipStream_t)stream, t, size);
+  vts_set_kernel("patch_jobs_kernel");
   VTS_CHECK_LAUNCH("vts_patch_jobs");
   return VTS_OK;
 }
@@ -842,6 +850,7 @@ extern "C" int vts_patch_scatter_bwd(const float* dpatch, int dp_C, int dp_c0, i
   VTS_CHECK_ARG(dpatch && offx && offy && dsrc && P == N * P_per_img, "vts_patch_scatter_bwd: P must equal N*P_per_img");
   hipLaunchKernelGGL(patch_scatter_kernel, dim3(cdiv(W, 32), cdiv(H, 32), N), dim3(256), P_per_img * sizeof(int), (hipStream_t)stream,
                      dpatch, dp_C, dp_c0, C, offx, offy, P_per_img, size, dsrc, dns, H, W, accumulate);
+  vts_set_kernel("patch_scatter_kernel");
   VTS_CHECK_LAUNCH("vts_patch_scatter_bwd");
   return VTS_OK;
 }
@@ -854,6 +863,7 @@ static int g_post_impl(const float* g_out, const float* M, int N, int H, int W, 
   hipLaunchKernelGGL(g_post_kernel, dim3((unsigned)cdiv64(HW, 256), N), dim3(256), 0, (hipStream_t)stream, g_out, M, HW, scale_nz, rb, rs,
                      fake_I, fake_T, fake_T_nstride ? fake_T_nstride : 2 * HW, fake_N, aug_fake_I, aug_nstride ? aug_nstride : 3 * HW,
                      S, stack_S, stack_M, stack_nstride);
+  vts_set_kernel("g_post_kernel");
   VTS_CHECK_LAUNCH("vts_g_post");
   return VTS_OK;
 }
@@ -875,6 +885,7 @@ extern "C" int vts_diffaug_bs_mask(const float* x, const float* M, int N, int H,
   VTS_CHECK_ARG(x && rb && rs && aug, "vts_diffaug_bs_mask: bad args");
   const int64_t HW = (int64_t)H * W;
   hipLaunchKernelGGL(diffaug_kernel, dim3((unsigned)cdiv64(HW, 256), N), dim3(256), 0, (hipStream_t)stream, x, M, HW, rb, rs, aug);
+  vts_set_kernel("diffaug_kernel");
   VTS_CHECK_LAUNCH("vts_diffaug_bs_mask");
   return VTS_OK;
 }
@@ -886,6 +897,7 @@ extern "C" int vts_g_out_grad_pool(const float* d_fake_I, const float* d_fake_I_
   const int64_t HW = (int64_t)H * W;
   hipLaunchKernelGGL(g_out_grad_kernel, dim3((unsigned)cdiv64(HW, 256), N), dim3(256), 0, (hipStream_t)stream, d_fake_I, d_fake_T, M,
                      g_out, HW, d_raw, d_fake_I_coarse, H, W, (H + 1) / 2, (W + 1) / 2);
+  vts_set_kernel("g_out_grad_kernel");
   VTS_CHECK_LAUNCH("vts_g_out_grad");
   return VTS_OK;
 }
@@ -913,6 +925,7 @@ extern "C" int vts_diffaug_op(const float* x, int64_t x_ns, float* out, int64_t 
   }
   hipLaunchKernelGGL(diffaug_op_kernel, dim3((unsigned)cdiv64(HW, 256), N), dim3(256), 0, (hipStream_t)stream, x, x_ns, out, out_ns, C, H, W, op,
                      pf, pi0, pi1, noise, ws, M);
+  vts_set_kernel(op == 'c' ? "diffaug_mean_part_kernel+diffaug_op_kernel" : "diffaug_op_kernel");
   VTS_CHECK_LAUNCH("vts_diffaug_op");
   return VTS_OK;
 }
@@ -923,6 +936,7 @@ extern "C" int vts_pool_query(const float* images, float* store, const int* ret_
   if (N == 0 || elems == 0) return VTS_OK;
   hipLaunchKernelGGL(pool_query_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, (hipStream_t)stream, images, store, ret_slot, put_slot,
                      N, elems, out);
+  vts_set_kernel("pool_query_kernel");
   VTS_CHECK_LAUNCH("vts_pool_query");
   return VTS_OK;
 }
@@ -930,6 +944,7 @@ extern "C" int vts_pool_query(const float* images, float* store, const int* ret_
 extern "C" int vts_mask_mul(const float* x, const float* M, int N, int C, int HW, float* y, void* stream) {
   VTS_CHECK_ARG(x && M && y, "vts_mask_mul: bad args");
   hipLaunchKernelGGL(mask_mul_kernel, dim3(cdiv(HW, 256), C, N), dim3(256), 0, (hipStream_t)stream, x, M, C, (int64_t)HW, y);
+  vts_set_kernel("mask_mul_kernel");
   VTS_CHECK_LAUNCH("vts_mask_mul");
   return VTS_OK;
 }
@@ -937,6 +952,7 @@ extern "C" int vts_mask_mul(const float* x, const float* M, int N, int C, int HW
 extern "C" int vts_u8_expand(const uint8_t* src, int64_t n, int normalize, float* out, void* stream) {
   VTS_CHECK_ARG(src && out && n >= 1, "vts_u8_expand: bad args");
   hipLaunchKernelGGL(u8_expand_kernel, dim3((unsigned)cdiv64(n, 1024)), dim3(256), 0, (hipStream_t)stream, src, n, normalize, out);
+  vts_set_kernel("u8_expand_kernel");
   VTS_CHECK_LAUNCH("vts_u8_expand");
   return VTS_OK;
 }
@@ -947,12 +963,14 @@ extern "C" int vts_input_images_u8(const uint8_t* S, const uint8_t* I, const uin
   const uintptr_t al = reinterpret_cast<uintptr_t>(S) | reinterpret_cast<uintptr_t>(I) | reinterpret_cast<uintptr_t>(M);
   const uintptr_t al16 = reinterpret_cast<uintptr_t>(M_out) | reinterpret_cast<uintptr_t>(S_out) | reinterpret_cast<uintptr_t>(S_out2) |
                          reinterpret_cast<uintptr_t>(I_out);
-  if (HW % 4 == 0 && (al & 3) == 0 && (al16 & 15) == 0)
+  const bool vec = HW % 4 == 0 && (al & 3) == 0 && (al16 & 15) == 0;
+  if (vec)
     hipLaunchKernelGGL(input_images_u8_kernel<true>, dim3((unsigned)cdiv64(HW, 1024), N), dim3(256), 0, (hipStream_t)stream, S, I, M, HW, M_out,
                        S_out, S_out2, I_out);
   else
     hipLaunchKernelGGL(input_images_u8_kernel<false>, dim3((unsigned)cdiv64(HW, 1024), N), dim3(256), 0, (hipStream_t)stream, S, I, M, HW, M_out,
                        S_out, S_out2, I_out);
+  vts_set_kernel(vec ? "input_images_u8_kernel<true>" : "input_images_u8_kernel<false>");
   VTS_CHECK_LAUNCH("vts_input_images_u8");
   return VTS_OK;
 }
@@ -960,6 +978,7 @@ extern "C" int vts_input_images_u8(const uint8_t* S, const uint8_t* I, const uin
 extern "C" int vts_spe_grid(float* out, int64_t ons, int N, int H, int W, int dim, void* stream) {
   VTS_CHECK_ARG(out && dim >= 4 && dim % 2 == 0, "vts_spe_grid: dim must be even and >= 4");
   hipLaunchKernelGGL(spe_kernel, dim3(cdiv(W, 256), H, N), dim3(256), 0, (hipStream_t)stream, out, ons, H, W, dim);
+  vts_set_kernel("spe_kernel");
   VTS_CHECK_LAUNCH("vts_spe_grid");
   return VTS_OK;
 }
@@ -972,6 +991,7 @@ extern "C" int vts_mask_candidates(const float* M, int N, int H, int W, uint8_t*
   VTS_CHECK_LAUNCH("vts_mask_candidates");
   hipLaunchKernelGGL(mask_rowcount_kernel, dim3(Hc, N), dim3(64), 0, st, cand, Hc, Wc, row_count);
   hipLaunchKernelGGL(mask_prefix_kernel, dim3(N), dim3(64), 0, st, row_count, Hc);
+  vts_set_kernel("mask_cand_kernel+mask_rowcount_kernel+mask_prefix_kernel");
   VTS_CHECK_LAUNCH("vts_mask_candidates prefix");
   return VTS_OK;
 }
@@ -1014,6 +1034,7 @@ extern "C" int vts_mask_sample_ranks(const int* row_prefix, int N, int H, int K,
   VTS_CHECK_ARG(row_prefix && ranks && N >= 1 && H > 14 && K >= 1 && K <= 1024, "vts_mask_sample_ranks: bad args (K <= 1024)");
   hipLaunchKernelGGL(mask_sample_ranks_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, row_prefix, H - 14, K, (unsigned long long)seed,
                      (long long*)ranks);
+  vts_set_kernel("mask_sample_ranks_kernel");
   VTS_CHECK_LAUNCH("vts_mask_sample_ranks");
   return VTS_OK;
 }
@@ -1023,6 +1044,7 @@ extern "C" int vts_mask_select(const uint8_t* cand, const int* row_prefix, int N
   VTS_CHECK_ARG(cand && row_prefix && ranks && offx && offy && K >= 1, "vts_mask_select: bad args");
   hipLaunchKernelGGL(mask_select_kernel, dim3(K, N), dim3(64), 0, (hipStream_t)stream, cand, row_prefix, H - 14, W - 14, ranks, K, offx,
                      offy);
+  vts_set_kernel("mask_select_kernel");
   VTS_CHECK_LAUNCH("vts_mask_select");
   return VTS_OK;
 }
@@ -1033,6 +1055,7 @@ extern "C" int vts_adam_flat(float* p, const float* g, float* m, float* v, int64
   const double bc1 = 1.0 - pow((double)beta1, step_count), bc2 = 1.0 - pow((double)beta2, step_count);
   hipLaunchKernelGGL(adam_kernel, dim3(blocks_for(n, 1024)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, (float)(lr / bc1), beta1,
                      beta2, eps, (float)(1.0 / sqrt(bc2)), grad_scale);
+  vts_set_kernel("adam_kernel");
   VTS_CHECK_LAUNCH("vts_adam_flat");
   return VTS_OK;
 }
@@ -1042,6 +1065,7 @@ extern "C" int vts_adam_flat_dev(float* p, const float* g, float* m, float* v, i
   VTS_CHECK_ARG(p && g && m && v && lr_dev && step_dev && n >= 1, "vts_adam_flat_dev: bad args");
   hipLaunchKernelGGL(adam_dev_kernel, dim3(blocks_for(n, 1024)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr_dev, beta1, beta2,
                      eps, step_dev, grad_scale);
+  vts_set_kernel("adam_dev_kernel");
   VTS_CHECK_LAUNCH("vts_adam_flat_dev");
   return VTS_OK;
 }
@@ -1049,6 +1073,7 @@ extern "C" int vts_adam_flat_dev(float* p, const float* g, float* m, float* v, i
 extern "C" int vts_l2norm_rows(const float* x, int rows, int D, float* y, void* stream) {
   VTS_CHECK_ARG(x && y && rows >= 1 && D >= 1, "vts_l2norm_rows: bad args");
   hipLaunchKernelGGL(l2norm_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, x, D, y);
+  vts_set_kernel("l2norm_kernel");
   VTS_CHECK_LAUNCH("vts_l2norm_rows");
   return VTS_OK;
 }
@@ -1077,6 +1102,7 @@ extern "C" int vts_copy_words(const void* src, void* dst, int64_t nwords, void* 
   VTS_CHECK_ARG(src && dst && nwords >= 0, "vts_copy_words: bad args");
   if (nwords == 0) return VTS_OK;
   hipLaunchKernelGGL(copy_words_kernel, dim3(blocks_for(nwords, 1024)), dim3(256), 0, (hipStream_t)stream, (const int*)src, (int*)dst, nwords);
+  vts_set_kernel("copy_words_kernel");
   VTS_CHECK_LAUNCH("vts_copy_words");
   return VTS_OK;
 }

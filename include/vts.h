@@ -878,24 +878,35 @@ int vts_spectral_norm(const float* w, float* u, float* v, int Co, int K, int tra
 int vts_spectral_norm_bwd(const float* g, const float* w_sn, const float* u, const float* v, const float* sigma, int Co, int K, float* dw,
                           int accumulate, float* ws, int64_t ws_floats, void* stream);
 
-/* ---- CLIP ViT image tower, forward only (csrc/vts_vit.hip) -------------------------------------------------------------------------------
+/* ---- CLIP ViT image tower, forward and input-gradient backward (csrc/vts_vit.hip) -----------------------------------------------------
  * skitG's style code: the reference runs a frozen CLIP ViT-B/32 image encoder in half precision on the masked visual image at every
- * forward (reference models/skitG_model.py:484-489, 704-724, 1294-1296).  Precision regime of every entry below: weights and GEMM inputs
+ * forward (reference models/skitG_model.py:484-489, 704-724, 1294-1296); its vision-aided discriminator differentiates through the same
+ * frozen tower (the backward entries below; the discriminator's heads are not built).  Precision regime of every entry below: weights and GEMM inputs
  * are IEEE fp16 (passed as uint16_t bit patterns), every matrix product runs on v_mfma_f32_16x16x32_f16 with fp32 accumulation, and the
  * residual stream, LayerNorm statistics, softmax, biases and epilogues are evaluated in fp32.  Repeats are bit-identical (no float atomics;
  * split-K partials are reduced in a fixed order).
  *
  * vts_gemm_f16: C[M x N] = epilogue(A[M x K] W[N x K]^T + bias[N]), A / W / bias fp16 row-major (bias NULL: none).
  *   epilogue VTS_GEMM_NONE; VTS_GEMM_QUICKGELU: v * sigmoid(1.702 v); VTS_GEMM_RESIDUAL: out[m][n] += v (out fp32, read and written).
+ *   vts_gemm_f16_aux is the same call with an fp16 [M x N] side buffer `aux`: VTS_GEMM_QUICKGELU also writes the pre-activation v there
+ *   (aux NULL: not kept); VTS_GEMM_QUICKGELU_BWD reads the saved pre-activation h from it and gives v * QuickGELU'(h),
+ *   QuickGELU'(h) = s (1 + 1.702 h (1 - s)), s = sigmoid(1.702 h) -- the input gradient of c_proj carried through the activation.
  *   out_f16 0: out is float [M x N]; 1: out is fp16 [M x N] (round to nearest even; not with VTS_GEMM_RESIDUAL).
  *   Any M >= 1; K % 32 == 0 and N % 16 == 0, VTS_ERR_UNSUPPORTED otherwise.  A workgroup owns 32 output features over all M rows, so each
  *   weight element is fetched from memory once per call; narrow N splits K over up to 8 workgroups whose partials (ws,
  *   vts_gemm_f16_ws_floats(M, N, K) floats; 0 means ws may be NULL) a second launch sums in split order.
  * vts_layernorm_rows: y[r] = (x[r] - mean) / sqrt(var + eps) * gamma + beta over rows of D fp32 values, x row r at x + r * x_stride
  *   (floats), y row r at r * D; biased variance, two-pass fp32 statistics; gamma / beta fp16 [D]; out_f16 as above.
+ * vts_layernorm_rows_bwd: the input gradient of vts_layernorm_rows (no gamma / beta gradients: the tower is frozen).  dy fp32 [rows][D],
+ *   x the saved fp32 rows (row r at x + r * x_stride), statistics recomputed from it: xh = (x - mean) rstd, a = gamma dy,
+ *   dx = rstd (a - mean(a) - xh mean(a xh)), written to dx + r * dx_stride, or added to what is there when accumulate != 0 (the
+ *   residual-gradient stream; ln_post's class-token rows use stride T * D).  dx16 (may be NULL): the value dx then holds, fp16 [rows][D].
  * vts_vit_attention: nn.MultiheadAttention's unmasked self-attention core on the packed projection qkv fp16 [B*T][3*heads*64]
  *   (q | k | v, each heads x 64): out[b*T + t][h*64 + :] = softmax(q_h k_h^T / 8) v_h, fp16 [B*T][heads*64].  Scores and softmax fp32,
  *   one workgroup per (image, head), one wave per 16 queries.  Head dimension 64 and 1 <= T <= 64 only (ViT-B/32 at 224^2: T = 50); VTS_ERR_UNSUPPORTED otherwise.
+ * vts_vit_attention_bwd: its backward.  dout fp16 [B*T][heads*64], dqkv fp16 [B*T][3*heads*64] in qkv's own layout (the next GEMM's
+ *   operand).  P is recomputed from qkv in fp32 as the forward forms it; dV = P^T dO, dP = dO V^T, dS = P o (dP - rowsum(dP o P)),
+ *   dQ = dS K / 8, dK = dS^T Q / 8, all five on the f16 MFMAs, P and dS entering theirs as two fp16 terms.  Same shapes as the forward.
  * vts_clip_preprocess: CLIP's transform ToPILImage -> Resize(224, BICUBIC) -> CenterCrop(224) -> ToTensor -> Normalize -> .half() of an
  *   fp32 [N][3][H][W] image, bit-exact with the host chain: byte = trunc(x * 255) mod 256 (ToPILImage's mul(255).byte(), which wraps
  *   negative values), Pillow's two 22-bit fixed-point passes (horizontal to uint8, then vertical to uint8) and a 3 x 256 lookup table
@@ -916,25 +927,64 @@ int vts_spectral_norm_bwd(const float* g, const float* w_sn, const float* u, con
  *   ws     vts_clip_visual_forward_ws_floats(cfg, N) floats (-1 on a bad config), 16-byte aligned
  *   Requires width == 64 * heads, T <= 64, width % 32 == 0, width <= 1024, output_dim % 16 == 0, resolution % patch == 0 and (3*patch*patch) % 32 == 0
  *   (the text tower and the other CLIP image towers are out of scope: VTS_ERR_UNSUPPORTED).  No allocation, no host synchronisation,
- *   every launch on `stream`: the call can be captured into a graph. */
+ *   every launch on `stream`: the call can be captured into a graph.
+ * vts_clip_visual_forward_tape: the same computation (out is bit-identical) that also fills `tape`, vts_clip_visual_tape_floats(cfg, N)
+ *   floats, 16-byte aligned, M = N * T rows:
+ *     [layers + 1][M][W] fp32   the residual stream after ln_pre (index 0) and after block l (index l): a "tap" is a slice of this;
+ *     [M][W] fp32               the stream before ln_pre;
+ *     per layer: [M][W] fp32 the stream between the block's two halves, [M][3W] fp16 the packed qkv, [M][4W] fp16 c_fc's output before QuickGELU.
+ * vts_clip_visual_backward: the frozen tower's input gradient, dx fp32 [N][3][resolution][resolution], with respect to the fp16 input of
+ *   the taped forward.  Cotangents: d_out fp32 [N][output_dim] (may be NULL) and d_hidden fp32 [n_taps][M][W] for the tape indices
+ *   taps[0] < taps[1] < ... (a HOST array, each 0 .. layers; n_taps may be 0); at least one of the two.  No parameter gradients; the class
+ *   and positional embeddings' gradients are not formed.  w is the forward's buffer (the LayerNorm gains); wt a second flat fp16 buffer
+ *   with every matrix transposed, so that the same GEMM kernel forms dX = dY W:
+ *     conv1.weight^T [3*patch*patch][W]; per layer: in_proj_weight^T [W][3W], out_proj.weight^T [W][W], c_fc.weight^T [W][4W],
+ *     c_proj.weight^T [4W][W]; proj [W][output_dim rounded up to 32, zero-filled];   vts_clip_visual_weight_t_halfs(cfg) halfs in all.
+ *   The cotangents are multiplied on the way in by a power of two found on the device (their largest magnitude goes to [1, 2)) and dx
+ *   is divided by it: fp16 operands lose nothing to the size of a GAN loss's gradients, and a scaled cotangent gives the scaled dx.
+ *   ws: vts_clip_visual_backward_ws_floats(cfg, N) floats.  VTS_ERR_UNSUPPORTED exactly where the forward reports it; no allocation, no
+ *   host synchronisation, no float atomics (repeats are bit-identical), every launch on `stream`.
+ * vts_clip_area_preprocess: the differentiable front end of that gradient path (CLIP's own transform goes through 8-bit Pillow and has
+ *   none): fp32 [N][3][H][W] in [-1, 1] -> x * 0.5 + 0.5 -> adaptive average pooling to res x res with the windows of torch's
+ *   F.interpolate(mode='area') (rows floor(i H / res) .. ceil((i + 1) H / res); any H, W, upscaling included) -> (v - mean_c) / std_c;
+ *   out fp32 or fp16 [N][3][res][res] (out_f16; the fp16 value is the fp32 value rounded).  vts_clip_area_preprocess_bwd: dy fp32
+ *   [N][3][res][res] -> dx fp32 [N][3][H][W] in gather form (no atomics), the fp16 rounding taken as the identity.  This is the form the
+ *   published vision-aided wrapper is understood to use; the package is not available, so it is PARITY UNPINNED against it and pinned
+ *   only to torch's own operator. */
 #define VTS_GEMM_NONE 0
 #define VTS_GEMM_QUICKGELU 1
 #define VTS_GEMM_RESIDUAL 2
+#define VTS_GEMM_QUICKGELU_BWD 3
 typedef struct vts_clip_visual_cfg {
   int width, layers, heads, patch, resolution, output_dim;
 } vts_clip_visual_cfg;
 int64_t vts_gemm_f16_ws_floats(int M, int N, int K);
 int vts_gemm_f16(const uint16_t* A, const uint16_t* W, const uint16_t* bias, int M, int N, int K, int epilogue, void* out, int out_f16,
                  float* ws, int64_t ws_floats, void* stream);
+int vts_gemm_f16_aux(const uint16_t* A, const uint16_t* W, const uint16_t* bias, int M, int N, int K, int epilogue, void* out, int out_f16,
+                     uint16_t* aux, float* ws, int64_t ws_floats, void* stream);
 int vts_layernorm_rows(const float* x, int64_t x_stride, int rows, int D, const uint16_t* gamma, const uint16_t* beta, float eps, void* y,
                        int out_f16, void* stream);
+int vts_layernorm_rows_bwd(const float* dy, const float* x, int64_t x_stride, int rows, int D, const uint16_t* gamma, float eps, float* dx,
+                           int64_t dx_stride, int accumulate, uint16_t* dx16, void* stream);
 int vts_vit_attention(const uint16_t* qkv, int B, int T, int heads, int head_dim, uint16_t* out, void* stream);
+int vts_vit_attention_bwd(const uint16_t* qkv, const uint16_t* dout, int B, int T, int heads, int head_dim, uint16_t* dqkv, void* stream);
 int vts_clip_preprocess(const float* x, int N, int H, int W, const int* hb, const int* hk, int hks, const int* vb, const int* vk, int vks,
                         const uint16_t* lut, uint8_t* tmp, uint16_t* out, void* stream);
 int64_t vts_clip_visual_weight_halfs(const vts_clip_visual_cfg* cfg);
 int64_t vts_clip_visual_forward_ws_floats(const vts_clip_visual_cfg* cfg, int N);
 int vts_clip_visual_forward(const vts_clip_visual_cfg* cfg, const uint16_t* w, const uint16_t* x, int N, float* out, float* ws,
                             int64_t ws_floats, void* stream);
+int64_t vts_clip_visual_tape_floats(const vts_clip_visual_cfg* cfg, int N);
+int vts_clip_visual_forward_tape(const vts_clip_visual_cfg* cfg, const uint16_t* w, const uint16_t* x, int N, float* out, float* ws,
+                                 int64_t ws_floats, float* tape, int64_t tape_floats, void* stream);
+int64_t vts_clip_visual_weight_t_halfs(const vts_clip_visual_cfg* cfg);
+int64_t vts_clip_visual_backward_ws_floats(const vts_clip_visual_cfg* cfg, int N);
+int vts_clip_visual_backward(const vts_clip_visual_cfg* cfg, const uint16_t* w, const uint16_t* wt, const float* tape, int64_t tape_floats, int N,
+                             const float* d_out, const int* taps, int n_taps, const float* d_hidden, float* dx, float* ws, int64_t ws_floats,
+                             void* stream);
+int vts_clip_area_preprocess(const float* x, int N, int H, int W, int res, void* out, int out_f16, void* stream);
+int vts_clip_area_preprocess_bwd(const float* dy, int N, int H, int W, int res, float* dx, void* stream);
 
 #ifdef __cplusplus
 }

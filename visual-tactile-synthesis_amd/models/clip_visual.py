@@ -1,4 +1,4 @@
-"""ClipVisual: CLIP's image tower (ViT-B/32 by default), frozen, forward only -- skitG's style encoder.
+"""ClipVisual: CLIP's image tower (ViT-B/32 by default), frozen -- skitG's style encoder, and a differentiable feature extractor.
 
 The reference derives the style code on every forward with `clip.load("ViT-B/32")`'s `.visual` in half precision (reference
 models/skitG_model.py:484-489, 1294-1296).  This module carries the same parameters under the names of CLIP's `VisionTransformer`
@@ -11,9 +11,15 @@ The published weights cannot exist offline: `--clip_weights <file>` (or $VTS_CLI
 a seeded stand-in (CLIP's own initialisation scales) and `pretrained` stays False -- style codes then compare builds on the same seed only,
 the precedent of `loss_lpips_pretrained` in models/perceptual.py.
 
-Out of scope (the library reports them): any backward pass (the tower is frozen and nothing differentiates through it; the vision-aided
-discriminator D3 would need it, plus CLIP's multi-level heads), the text tower, and the other CLIP architectures (only head dimension 64
-and at most 64 tokens are built).
+The tower is frozen, but an image can be differentiated THROUGH it: `features` returns the embedding and any blocks' hidden states of an
+image of any size (area pooling + CLIP's normalisation, ops.clip_area_preprocess: CLIP's own transform goes through 8-bit Pillow and has
+no gradient), and `features_backward` takes cotangents of those back to the image (vts_clip_visual_forward_tape /
+vts_clip_visual_backward: input gradient only, no parameter gradients).  That is the half of the reference's vision-aided discriminator
+D3 that can be built here.
+
+Out of scope (the library reports them): D3's multi-level heads -- small convolutions on the tapped hidden states, defined by a
+third-party package whose source is not available, so they cannot be pinned and the models still refuse `--use_vision_aided_loss True`
+at the warm-up epoch --, the text tower, and the other CLIP architectures (only head dimension 64 and at most 64 tokens are built).
 """
 import os
 
@@ -104,16 +110,18 @@ class ClipVisual(nn.Module):
         self.proj = nn.Parameter(torch.zeros(w, self.cfg["output_dim"]), requires_grad=False)
         self.pretrained = False
         self._flat, self._ws = None, {}
+        self._flat_t, self._bwd = None, {}
         self.load_state_dict(standin_state(self.cfg, seed))
         self.eval()
 
     def load_state_dict(self, sd, strict=True, **kw):
         out = super().load_state_dict(sd, strict=strict, **kw)
-        self._flat = None
+        self._flat, self._flat_t, self._bwd = None, None, {}
         return out
 
     def _apply(self, fn, *a, **kw):
         self._flat, self._ws = None, {}
+        self._flat_t, self._bwd = None, {}
         return super()._apply(fn, *a, **kw)
 
     def load_weights(self, path):
@@ -160,6 +168,67 @@ class ClipVisual(nn.Module):
             self._flat = torch.cat([p.reshape(-1).to(torch.float16) for p in parts]).contiguous()
             self._ccfg = ops.clip_visual_cfg(**self.cfg)
         return self._flat
+
+    def flat_weights_t(self):
+        """the second flat fp16 buffer, every matrix transposed (include/vts.h: vts_clip_visual_backward), so that the forward's GEMM
+        kernel forms the input gradients; built on the first backward only"""
+        if self._flat_t is None:
+            sd, w = self.state_dict(), self.cfg["width"]
+            parts = [sd["conv1.weight"].reshape(w, -1).t()]
+            for i in range(self.cfg["layers"]):
+                p = "transformer.resblocks.%d." % i
+                parts += [sd[p + k].t() for k in ("attn.in_proj_weight", "attn.out_proj.weight", "mlp.c_fc.weight", "mlp.c_proj.weight")]
+            od = self.cfg["output_dim"]
+            parts.append(torch.nn.functional.pad(sd["proj"], (0, -od % 32)))
+            self._flat_t = torch.cat([p.reshape(-1).to(torch.float16) for p in parts]).contiguous()
+        return self._flat_t
+
+    def _backward_buffers(self, n, device):
+        """(tape, forward scratch, backward scratch) of batch size n: the tower's own, allocated on first use"""
+        b = self._bwd.get(n)
+        if b is None:
+            self.flat_weights()
+            b = self._bwd[n] = tuple(torch.empty(k, dtype=torch.float32, device=device) for k in (
+                ops.clip_visual_tape_floats(self._ccfg, n), ops.clip_visual_forward_ws_floats(self._ccfg, n),
+                ops.clip_visual_backward_ws_floats(self._ccfg, n)))
+        return b
+
+    def forward_taped(self, x16, taps=()):
+        """x16: fp16 [N, 3, res, res] -> (embedding fp32 [N, output_dim], [hidden state after block l, fp32 [N, T, W], for l in taps],
+        ctx).  The hidden states are views into the tape of this batch size: the next taped forward of that size overwrites them."""
+        if not x16.is_cuda:
+            raise RuntimeError("ClipVisual: HIP path only (the tower runs through vts_clip_visual_forward_tape); input is on %s" % x16.device)
+        taps = tuple(int(t) for t in taps)
+        if any(t < 1 or t > self.cfg["layers"] for t in taps) or list(taps) != sorted(set(taps)):
+            raise ValueError("ClipVisual: taps %s must be ascending block numbers in 1 .. %d" % (taps, self.cfg["layers"]))
+        flat, n = self.flat_weights(), x16.shape[0]
+        tape, ws, _ = self._backward_buffers(n, x16.device)
+        emb = ops.clip_visual_forward_tape(self._ccfg, flat, x16, tape, ws=ws)
+        return emb, [ops.clip_visual_hidden(self._ccfg, tape, n, t) for t in taps], {"n": n, "taps": taps}
+
+    def input_gradient(self, ctx, d_embedding=None, d_hidden=()):
+        """cotangents of forward_taped's results (d_hidden: one per tap, in order; either may be absent, not both) -> the gradient with
+        respect to x16, fp32 [N, 3, res, res]"""
+        taps = ctx["taps"] if len(d_hidden) else ()
+        if len(d_hidden) != len(taps):
+            raise ValueError("ClipVisual: %d hidden cotangents for taps %s" % (len(d_hidden), ctx["taps"]))
+        tape, _, ws = self._backward_buffers(ctx["n"], self._flat.device)
+        dh = torch.stack([d.to(torch.float32) for d in d_hidden]).contiguous() if taps else None
+        de = None if d_embedding is None else d_embedding.to(torch.float32).contiguous()
+        return ops.clip_visual_backward(self._ccfg, self._flat, self.flat_weights_t(), tape, ctx["n"], d_out=de, taps=taps, d_hidden=dh, ws=ws)
+
+    def features(self, image, taps=()):
+        """image fp32 [N, 3, H, W] in [-1, 1], any size -> (embedding, [hidden states of the blocks in taps], ctx), differentiable with
+        features_backward: area pooling to the tower's resolution and CLIP's normalisation (ops.clip_area_preprocess), then forward_taped"""
+        if not image.is_cuda:
+            raise RuntimeError("ClipVisual: HIP path only (the tower runs through vts_clip_visual_forward_tape); input is on %s" % image.device)
+        emb, hidden, ctx = self.forward_taped(ops.clip_area_preprocess(image.contiguous(), self.cfg["resolution"]), taps)
+        ctx["hw"] = tuple(image.shape[2:])
+        return emb, hidden, ctx
+
+    def features_backward(self, ctx, d_embedding=None, d_hidden=()):
+        """-> d_image fp32 [N, 3, H, W]"""
+        return ops.clip_area_preprocess_bwd(self.input_gradient(ctx, d_embedding, d_hidden), *ctx["hw"])
 
     def forward(self, x, out=None):
         """x: fp16 [N, 3, res, res] (ops.clip_preprocess's output) -> fp32 [N, output_dim]"""

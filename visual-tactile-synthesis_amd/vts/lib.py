@@ -165,6 +165,9 @@ SYMBOLS = [
     "vts_spectral_norm_ws_floats", "vts_spectral_norm", "vts_spectral_norm_bwd", "vts_tanh_bwd", "vts_spade_eval_stats",
     "vts_gemm_f16_ws_floats", "vts_gemm_f16", "vts_layernorm_rows", "vts_vit_attention", "vts_clip_preprocess", "vts_clip_visual_weight_halfs",
     "vts_clip_visual_forward_ws_floats", "vts_clip_visual_forward",
+    "vts_gemm_f16_aux", "vts_layernorm_rows_bwd", "vts_vit_attention_bwd", "vts_clip_visual_tape_floats", "vts_clip_visual_forward_tape",
+    "vts_clip_visual_weight_t_halfs", "vts_clip_visual_backward_ws_floats", "vts_clip_visual_backward", "vts_clip_area_preprocess",
+    "vts_clip_area_preprocess_bwd",
 ]
 
 
@@ -228,6 +231,11 @@ def load():
     lib.vts_clip_visual_weight_halfs.restype = C.c_int64
     lib.vts_clip_visual_forward_ws_floats.argtypes = [C.POINTER(ClipVisualCfg), C.c_int]
     lib.vts_clip_visual_forward_ws_floats.restype = C.c_int64
+    lib.vts_clip_visual_weight_t_halfs.argtypes = [C.POINTER(ClipVisualCfg)]
+    lib.vts_clip_visual_weight_t_halfs.restype = C.c_int64
+    for name in ("vts_clip_visual_tape_floats", "vts_clip_visual_backward_ws_floats"):
+        getattr(lib, name).argtypes = [C.POINTER(ClipVisualCfg), C.c_int]
+        getattr(lib, name).restype = C.c_int64
     vp, i, i64, f = C.c_void_p, C.c_int, C.c_int64, C.c_float
     sig = {
         "vts_conv4x4": [C.POINTER(ConvDesc), vp],
@@ -341,6 +349,13 @@ def load():
         "vts_vit_attention": [vp, i, i, i, i, vp, vp],
         "vts_clip_preprocess": [vp, i, i, i, vp, vp, i, vp, vp, i, vp, vp, vp, vp],
         "vts_clip_visual_forward": [C.POINTER(ClipVisualCfg), vp, vp, i, vp, vp, i64, vp],
+        "vts_gemm_f16_aux": [vp, vp, vp, i, i, i, i, vp, i, vp, vp, i64, vp],
+        "vts_layernorm_rows_bwd": [vp, vp, i64, i, i, vp, f, vp, i64, i, vp, vp],
+        "vts_vit_attention_bwd": [vp, vp, i, i, i, i, vp, vp],
+        "vts_clip_visual_forward_tape": [C.POINTER(ClipVisualCfg), vp, vp, i, vp, vp, i64, vp, i64, vp],
+        "vts_clip_visual_backward": [C.POINTER(ClipVisualCfg), vp, vp, vp, i64, i, vp, C.POINTER(C.c_int), i, vp, vp, vp, i64, vp],
+        "vts_clip_area_preprocess": [vp, i, i, i, i, vp, i, vp],
+        "vts_clip_area_preprocess_bwd": [vp, i, i, i, i, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)

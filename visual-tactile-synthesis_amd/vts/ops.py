@@ -1721,13 +1721,14 @@ def spade_eval_stats(running_mean, running_var, n, eps=1e-5):
     return st[0], st[1]
 
 
-# ---- CLIP ViT image tower (include/vts.h "CLIP ViT image tower", csrc/vts_vit.hip): skitG's style encoder, forward only ----
-GEMM_EPILOGUES = {"none": 0, "quickgelu": 1, "residual": 2}
+# ---- CLIP ViT image tower (include/vts.h "CLIP ViT image tower", csrc/vts_vit.hip): skitG's style encoder, and its input-gradient backward ----
+GEMM_EPILOGUES = {"none": 0, "quickgelu": 1, "residual": 2, "quickgelu_bwd": 3}
 
 
-def gemm_f16(a, w, bias=None, epilogue="none", out=None, out_dtype=torch.float32):
+def gemm_f16(a, w, bias=None, epilogue="none", out=None, out_dtype=torch.float32, aux=None):
     """epilogue(a [M, K] @ w [N, K]^T + bias [N]) on the f16 MFMAs with fp32 accumulation; a / w / bias fp16.  `residual` adds into the
-    fp32 `out`; otherwise out is fp32 or fp16 (`out_dtype`)."""
+    fp32 `out`; otherwise out is fp32 or fp16 (`out_dtype`).  `aux` fp16 [M, N]: `quickgelu` also leaves its pre-activation there,
+    `quickgelu_bwd` reads it and multiplies the product by QuickGELU'(aux)."""
     m, k = a.shape
     n = w.shape[0]
     assert a.dtype == w.dtype == torch.float16 and w.shape[1] == k and a.is_contiguous() and w.is_contiguous()
@@ -1739,6 +1740,11 @@ def gemm_f16(a, w, bias=None, epilogue="none", out=None, out_dtype=torch.float32
     lib = L.load()
     nws = lib.vts_gemm_f16_ws_floats(m, n, k)
     ws = workspace(nws, a.device) if nws else None
+    if aux is not None or epilogue == "quickgelu_bwd":
+        assert aux is not None and aux.dtype == torch.float16 and tuple(aux.shape) == (m, n) and aux.is_contiguous()
+        _run("gemm_f16", 2.0 * (m * k + n * k) + (2 + out.element_size()) * m * n, 2.0 * m * n * k, lib.vts_gemm_f16_aux, a.data_ptr(), w.data_ptr(),
+             L.ptr(bias), m, n, k, GEMM_EPILOGUES[epilogue], out.data_ptr(), int(out.dtype == torch.float16), aux.data_ptr(), L.ptr(ws), nws, L.stream())
+        return out
     _run("gemm_f16", 2.0 * (m * k + n * k) + out.element_size() * m * n, 2.0 * m * n * k, lib.vts_gemm_f16, a.data_ptr(), w.data_ptr(), L.ptr(bias),
          m, n, k, GEMM_EPILOGUES[epilogue], out.data_ptr(), int(out.dtype == torch.float16), L.ptr(ws), nws, L.stream())
     return out
@@ -1752,6 +1758,35 @@ def layernorm_rows(x, gamma, beta, eps=1e-5, out_dtype=torch.float32):
     _run("layernorm_rows", 4.0 * rows * d + y.element_size() * rows * d, 8.0 * rows * d, L.load().vts_layernorm_rows, x.data_ptr(), x.stride(0), rows, d,
          gamma.data_ptr(), beta.data_ptr(), eps, y.data_ptr(), int(out_dtype == torch.float16), L.stream())
     return y
+
+
+def layernorm_rows_bwd(dy, x, gamma, eps=1e-5, out=None, accumulate=False, half_out=False):
+    """input gradient of layernorm_rows: dy fp32 [rows, D] contiguous, x the fp32 rows the forward read (any row stride), gamma fp16 [D].
+    `out` fp32 [rows, D] (any row stride; a new tensor when None) receives dx, or dx is added to it (`accumulate`); `half_out` also returns
+    the value `out` then holds as fp16 [rows, D]."""
+    rows, d = x.shape
+    assert dy.dtype == x.dtype == torch.float32 and tuple(dy.shape) == (rows, d) and dy.is_contiguous() and x.stride(1) == 1
+    assert gamma.dtype == torch.float16 and gamma.numel() == d
+    if out is None:
+        assert not accumulate, "accumulate adds into `out`"
+        out = torch.empty(rows, d, dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (rows, d) and out.stride(1) == 1
+    o16 = torch.empty(rows, d, dtype=torch.float16, device=x.device) if half_out else None
+    _run("layernorm_rows_bwd", 4.0 * rows * d * (4 if accumulate else 3), 12.0 * rows * d, L.load().vts_layernorm_rows_bwd, dy.data_ptr(), x.data_ptr(),
+         x.stride(0), rows, d, gamma.data_ptr(), eps, out.data_ptr(), out.stride(0), int(accumulate), L.ptr(o16), L.stream())
+    return (out, o16) if half_out else out
+
+
+def vit_attention_bwd(qkv, dout, batch, tokens, heads):
+    """backward of vit_attention: qkv fp16 [batch * tokens, 3 * heads * 64] as the forward read it, dout fp16 [batch * tokens, heads * 64]
+    -> dqkv fp16 in qkv's layout"""
+    assert qkv.dtype == dout.dtype == torch.float16 and qkv.is_contiguous() and dout.is_contiguous()
+    assert qkv.shape[0] == dout.shape[0] == batch * tokens and qkv.shape[1] == 3 * dout.shape[1] and dout.shape[1] % heads == 0
+    hd = dout.shape[1] // heads
+    dqkv = torch.empty_like(qkv)
+    _run("vit_attention_bwd", 2.0 * (2 * qkv.numel() + dout.numel()), 10.0 * batch * heads * tokens * tokens * hd, L.load().vts_vit_attention_bwd,
+         qkv.data_ptr(), dout.data_ptr(), batch, tokens, heads, hd, dqkv.data_ptr(), L.stream())
+    return dqkv
 
 
 def vit_attention(qkv, batch, tokens, heads):
@@ -1874,3 +1909,99 @@ def clip_visual_forward(cfg, wbuf, x, out=None, ws=None):
     _run("clip_visual_forward", 2.0 * (wbuf.numel() + x.numel()), flops, lib.vts_clip_visual_forward, C.byref(cfg), wbuf.data_ptr(), x.data_ptr(), n,
          out.data_ptr(), ws.data_ptr(), ws.numel(), L.stream())
     return out
+
+
+def _clip_size(fn, what, cfg, *a):
+    n = fn(C.byref(cfg), *a)
+    if n < 0:
+        raise RuntimeError("%s: %s" % (what, L.load().vts_last_error().decode()))
+    return n
+
+
+def clip_visual_tape_floats(cfg, n):
+    return _clip_size(L.load().vts_clip_visual_tape_floats, "vts_clip_visual_forward_tape", cfg, n)
+
+
+def clip_visual_weight_t_halfs(cfg):
+    return _clip_size(L.load().vts_clip_visual_weight_t_halfs, "vts_clip_visual_weight_t_halfs", cfg)
+
+
+def clip_visual_backward_ws_floats(cfg, n):
+    return _clip_size(L.load().vts_clip_visual_backward_ws_floats, "vts_clip_visual_backward", cfg, n)
+
+
+def _clip_flops(cfg, n):
+    t = (cfg.resolution // cfg.patch) ** 2 + 1
+    return 2.0 * n * ((t - 1) * cfg.width * 3 * cfg.patch ** 2 + cfg.layers * t * (12 * cfg.width ** 2 + 2 * t * cfg.width) + cfg.width * cfg.output_dim)
+
+
+def clip_visual_forward_tape(cfg, wbuf, x, tape, out=None, ws=None):
+    """clip_visual_forward that also fills `tape` (fp32, clip_visual_tape_floats(cfg, N) floats; include/vts.h documents the layout) with
+    what clip_visual_backward reads; `out` is bit-identical to clip_visual_forward's"""
+    n = x.shape[0]
+    assert x.dtype == wbuf.dtype == torch.float16 and x.is_contiguous() and wbuf.is_contiguous() and tape.dtype == torch.float32 and tape.is_contiguous()
+    assert tuple(x.shape) == (n, 3, cfg.resolution, cfg.resolution), tuple(x.shape)
+    assert wbuf.numel() == clip_visual_weight_halfs(cfg), (wbuf.numel(), clip_visual_weight_halfs(cfg))
+    if ws is None:
+        ws = workspace(clip_visual_forward_ws_floats(cfg, n), x.device)
+    if out is None:
+        out = torch.empty(n, cfg.output_dim, dtype=torch.float32, device=x.device)
+    assert tuple(out.shape) == (n, cfg.output_dim) and out.dtype == torch.float32 and out.is_contiguous()
+    _run("clip_visual_forward_tape", 2.0 * (wbuf.numel() + x.numel()) + 4.0 * tape.numel(), _clip_flops(cfg, n), L.load().vts_clip_visual_forward_tape,
+         C.byref(cfg), wbuf.data_ptr(), x.data_ptr(), n, out.data_ptr(), ws.data_ptr(), ws.numel(), tape.data_ptr(), tape.numel(), L.stream())
+    return out
+
+
+def clip_visual_hidden(cfg, tape, n, index):
+    """the fp32 residual stream [N, T, W] after ln_pre (index 0) or after block `index`: a view into the tape"""
+    t = (cfg.resolution // cfg.patch) ** 2 + 1
+    mw = n * t * cfg.width
+    return tape[index * mw:(index + 1) * mw].view(n, t, cfg.width)
+
+
+def clip_visual_backward(cfg, wbuf, wtbuf, tape, n, d_out=None, taps=(), d_hidden=None, dx=None, ws=None):
+    """the frozen tower's input gradient: cotangents d_out fp32 [N, output_dim] (or None) and d_hidden fp32 [len(taps), N, T, W] for the
+    ascending tape indices `taps` -> dx fp32 [N, 3, res, res] (include/vts.h: vts_clip_visual_backward)"""
+    assert wbuf.dtype == wtbuf.dtype == torch.float16 and wbuf.is_contiguous() and wtbuf.is_contiguous() and tape.dtype == torch.float32
+    assert wtbuf.numel() == clip_visual_weight_t_halfs(cfg), (wtbuf.numel(), clip_visual_weight_t_halfs(cfg))
+    t = (cfg.resolution // cfg.patch) ** 2 + 1
+    assert d_out is None or (d_out.dtype == torch.float32 and d_out.is_contiguous() and tuple(d_out.shape) == (n, cfg.output_dim))
+    taps = [int(v) for v in taps]
+    if taps:
+        assert d_hidden is not None and d_hidden.dtype == torch.float32 and d_hidden.is_contiguous()
+        assert tuple(d_hidden.shape) == (len(taps), n, t, cfg.width), tuple(d_hidden.shape)
+    if ws is None:
+        ws = workspace(clip_visual_backward_ws_floats(cfg, n), tape.device)
+    if dx is None:
+        dx = torch.empty(n, 3, cfg.resolution, cfg.resolution, dtype=torch.float32, device=tape.device)
+    assert tuple(dx.shape) == (n, 3, cfg.resolution, cfg.resolution) and dx.dtype == torch.float32 and dx.is_contiguous()
+    ctaps = (C.c_int * max(len(taps), 1))(*taps)
+    _run("clip_visual_backward", 2.0 * wtbuf.numel() + 4.0 * (tape.numel() + dx.numel()), _clip_flops(cfg, n), L.load().vts_clip_visual_backward,
+         C.byref(cfg), wbuf.data_ptr(), wtbuf.data_ptr(), tape.data_ptr(), tape.numel(), n, L.ptr(d_out), ctaps, len(taps), L.ptr(d_hidden if taps else None),
+         dx.data_ptr(), ws.data_ptr(), ws.numel(), L.stream())
+    return dx
+
+
+def clip_area_preprocess(x, res=224, out=None, out_dtype=torch.float16):
+    """the differentiable front end: fp32 [N, 3, H, W] in [-1, 1] -> x * 0.5 + 0.5 -> F.interpolate(mode='area') to res x res -> CLIP's
+    normalisation, fp16 (the tower's input) or fp32"""
+    n, c, h, w = x.shape
+    assert c == 3 and x.dtype == torch.float32 and x.is_contiguous()
+    if out is None:
+        out = torch.empty(n, 3, res, res, dtype=out_dtype, device=x.device)
+    assert tuple(out.shape) == (n, 3, res, res) and out.dtype in (torch.float16, torch.float32) and out.is_contiguous()
+    _run("clip_area_preprocess", 4.0 * x.numel() + out.element_size() * out.numel(), 0.0, L.load().vts_clip_area_preprocess, x.data_ptr(), n, h, w, res,
+         out.data_ptr(), int(out.dtype == torch.float16), L.stream())
+    return out
+
+
+def clip_area_preprocess_bwd(dy, h, w, dx=None):
+    """its backward: dy fp32 [N, 3, res, res] -> fp32 [N, 3, h, w] (the fp16 rounding of the forward is taken as the identity)"""
+    n, c, res, res2 = dy.shape
+    assert c == 3 and res == res2 and dy.dtype == torch.float32 and dy.is_contiguous()
+    if dx is None:
+        dx = torch.empty(n, 3, h, w, dtype=torch.float32, device=dy.device)
+    assert tuple(dx.shape) == (n, 3, h, w) and dx.dtype == torch.float32 and dx.is_contiguous()
+    _run("clip_area_preprocess_bwd", 4.0 * (dy.numel() + dx.numel()), 0.0, L.load().vts_clip_area_preprocess_bwd, dy.data_ptr(), n, h, w, res,
+         dx.data_ptr(), L.stream())
+    return dx

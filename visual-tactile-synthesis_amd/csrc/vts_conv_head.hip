@@ -3,13 +3,11 @@
 //
 // On the 16 x 16 x 4 MFMA tiles of conv4x4_kernel one of the sixteen output-channel columns carries work: the 64 -> 1 head at
 // 131 x 131 took 78 us for 8 images, against 4.3 us of HBM time for its 34.6 MB input.  This layer is a 1024-term dot product per
-// output pixel, so it runs on the vector ALUs instead: a workgroup owns a 32 x 32 output tile, stages the 35 x 35 input patch of 8
-// channels at a time in LDS (normalise + LeakyReLU applied on the way, zero padding resolved there; the loads of the next chunk are
-// in flight in registers while the current one is multiplied), and a thread computes four horizontally adjacent outputs: per
-// channel and tap row two 16-byte LDS reads feed 16 FMAs with the four taps as a wave-uniform 16-byte broadcast read.
-// A 131 x 131 map has only 25 tiles per image, i.e. ~1 workgroup per CU: to have several waves per SIMD (LDS latency is otherwise
-// fully exposed: measured 65 us with 256 threads) the workgroup has 1024 threads -- four groups of 256 share the staged patch and
-// split the channels of a chunk; their partial sums are combined through LDS in group order at the end.
+// output pixel, so it runs on the vector ALUs.  Until round 13 a 1024-thread workgroup owned a 32 x 32 output tile and walked the
+// channels in 8 chunks of 8 through an LDS patch (load -> LDS -> barrier -> FMAs -> barrier per chunk): 28 us whatever the map size
+// (N4 34^2 .. N8 130^2: 27.7 - 29.8 us), the depth of that chain.  Now the lane = pixel form of vts_conv_px.hip (conv_head_kernel
+// below): no LDS patch, no barrier in the channel loop, and the time follows the map: 8.7 us (N4 34^2) .. 23.8 us (N8 130^2) where the
+// chunk-serial form took 24.0 .. 28.0 on the same box (one launch in a HIP graph, tools/mb_heads.py; profiles/r13_latency_floors.md).
 // Algorithmic bytes = 4 (in + out + w).  Exact fp32; the summation order over (channel, ky, kx) is fixed.
 #include <limits.h>
 #include <stdlib.h>
@@ -32,121 +30,129 @@ struct HeadK {
   const float* ident;
 };
 
-constexpr int HK_TY = 32, HK_TX = 32, HK_PR = HK_TY + 3, HK_PC = HK_TX + 3, HK_PCP = 36;
 constexpr int HK_MAXC = 512;
+constexpr int HK_T = 4;      // output rows per workgroup
+constexpr int HK_CU = 4;     // channels per load round of a wave
+constexpr int HK_VL = 61;    // output columns per workgroup: lane l loads input column x0 - pad + l, taps 1..3 come from lanes l + 1..3
 
-template <int CK>
-__global__ __launch_bounds__(1024) void conv_head_kernel(const HeadK p) {
-  constexpr int BLOCK = 1024, NG = BLOCK / 256, CPG = CK / NG;   // thread groups, channels of a chunk per group
-  static_assert(CK % NG == 0, "a chunk splits evenly over the thread groups");
-  constexpr int NEL = CK * HK_PR * HK_PC;            // staged elements per chunk
-  constexpr int NLD = (NEL + BLOCK - 1) / BLOCK;     // ... per thread
-  __shared__ __attribute__((aligned(16))) float tile[CK][HK_PR][HK_PCP];
-  __shared__ __attribute__((aligned(16))) float wl[CK][16];
-  __shared__ float ssc[HK_MAXC], ssh[HK_MAXC];
-  const int tid = threadIdx.x, n = blockIdx.z;
-  const int grp = __builtin_amdgcn_readfirstlane(tid >> 8), t256 = tid & 255;
-  const int tx4 = t256 & 7, ty = t256 >> 3;
-  const int oy0 = blockIdx.y * HK_TY, ox0 = blockIdx.x * HK_TX;
-  const int iy0 = oy0 - p.pad, ix0 = ox0 - p.padx;
-  for (int c = tid; c < p.C; c += BLOCK) {
-    ssc[c] = p.sc ? p.sc[n * p.C + c] : 1.f;
-    ssh[c] = p.sh ? p.sh[n * p.C + c] : 0.f;
-  }
-  // per-thread staging slots: element e = i * 256 + tid of the chunk -> (channel, row, column); fixed for all chunks
-  int soff[NLD], sdst[NLD];   // offset inside the chunk's planes (or -1: padding / beyond the patch), LDS word
-  const int64_t plane = (int64_t)p.IH * p.IW;
+typedef __amdgpu_buffer_rsrc_t rsrc_t;
+__device__ __forceinline__ float ld_buf(const rsrc_t& rs, unsigned voff, unsigned soff) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)voff, (int)soff, 0));
+}
+__device__ __forceinline__ float and_bits(float v, unsigned m) { return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) & m); }
+// whole-wave DPP shift: lane i <- lane i + 1, 0 at the open end (as in vts_conv_px.hip)
+__device__ __forceinline__ float from_next(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xF, 0xF, true));
+}
+
+// Lane = pixel form: a workgroup owns T output rows x 61 output columns of one image; its four waves split the channels (wave w takes
+// channels 2w, 2w + 1, 8 + 2w, 8 + 2w + 1, ...: the channels of partial sum w, see chan below) and keep T accumulators per lane.  Per channel a wave loads the T + 3 input rows of the tile as one coalesced
+// row load each (lane l = input column x0 - pad + l; row and column clamped into the map, so every load is unconditional and in
+// range), applies normalise + LeakyReLU once per loaded value and zeroes what lies outside the map with a mask, takes the three
+// neighbouring taps over whole-wave DPP shifts, and multiplies with the channel's 16 taps as wave-uniform scalars.  No LDS and no
+// barrier in the channel loop: the loads of the next CU channels are in flight while the current CU are multiplied.  The waves'
+// partial sums are combined through LDS once, in wave order.  hipcc packs the FMAs of two output rows into v_pk_fma_f32; 93 VGPRs.
+// The largest map (N8 130^2, 23.8 us = 1.48 TB/s) is bound by vector-ALU issue, not by HBM: 7 loaded rows per 4 output rows.
+template <int T, int CU>
+__global__ __launch_bounds__(256) void conv_head_kernel(const HeadK p) {
+  constexpr int R = T + 3;
+  static_assert(T % 4 == 0, "the four waves split the rows of the final combination");
+  __shared__ float red[4][T][64];
+  const int tid = threadIdx.x, lane = tid & 63, n = blockIdx.z;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int oy0 = blockIdx.y * T, ox0 = blockIdx.x * HK_VL;
+  const int iy0 = oy0 - p.pad, ix = ox0 - p.padx + lane;
+  const unsigned cmask = (ix >= 0 && ix < p.IW) ? 0xFFFFFFFFu : 0u;
+  const unsigned vo = (unsigned)min(max(ix, 0), p.IW - 1) * 4u;
+  unsigned so[R], rmask[R];   // wave-uniform: byte offset of the (clamped) input row inside a plane, all-ones where the row is inside the map
 #pragma unroll
-  for (int i = 0; i < NLD; ++i) {
-    const int e = i * BLOCK + tid;
-    const int c = e / (HK_PR * HK_PC), rem = e - c * (HK_PR * HK_PC);
-    const int r = rem / HK_PC, col = rem - r * HK_PC;
-    const int iy = iy0 + r, ix = ix0 + col;
-    const bool in = e < NEL && iy >= 0 && iy < p.IH && ix >= 0 && ix < p.IW;
-    soff[i] = in ? iy * p.IW + ix : -1;
-    sdst[i] = e < NEL ? (c * HK_PR + r) * HK_PCP + col : -1;
+  for (int r = 0; r < R; ++r) {
+    const int iy = iy0 + r;
+    so[r] = (unsigned)(min(max(iy, 0), p.IH - 1) * p.IW) * 4u;
+    rmask[r] = (iy >= 0 && iy < p.IH) ? 0xFFFFFFFFu : 0u;
   }
+  const int plane = p.IH * p.IW;
   const float* xb = p.x + n * p.ns;
-  float pv[NLD];
-  // chunk-local channel of slot i: BLOCK consecutive elements cross at most one channel boundary (a plane has 1225 of them)
-  static_assert(BLOCK <= HK_PR * HK_PC, "one boundary per slot");
-  auto chan = [&](int i) {
-    const int b = (i * BLOCK) / (HK_PR * HK_PC);
-    return b + (tid >= (b + 1) * (HK_PR * HK_PC) - i * BLOCK ? 1 : 0);
-  };
-  auto load_chunk = [&](int c0) {
+  // The wave's j-th channel.  The summation order per output is the one this kernel has had since round 2, so that results do not change
+  // with the form: four partial sums, partial sum g over the channels c with (c % 8) / 2 == g in ascending order (per channel ky, kx
+  // ascending, one fma chain), combined as ((s0 + s1) + s2) + s3, then the bias.  Wave g computes partial sum g.
+  auto chan = [&](int j) { return (j >> 1) * 8 + wv * 2 + (j & 1); };
+  const int nch = 2 * (p.C >> 3) + min(max((p.C & 7) - 2 * wv, 0), 2);     // channels of this wave: chan(j) < C exactly for j < nch
+  const int nround = (nch + CU - 1) / CU;
+  float acc[T];
 #pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int c = c0 + chan(i);
-      pv[i] = (soff[i] >= 0 && c < p.C) ? xb[c * plane + soff[i]] : 0.f;
+  for (int t = 0; t < T; ++t) acc[t] = 0.f;
+  float rawA[CU][R], rawB[CU][R];
+  auto load = [&](float (&raw)[CU][R], int round) {
+#pragma unroll
+    for (int u = 0; u < CU; ++u) {
+      const int c = min(chan(round * CU + u), p.C - 1);
+      const rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(xb + (int64_t)c * plane), 0, plane * 4, 0x00020000);
+#pragma unroll
+      for (int r = 0; r < R; ++r) raw[u][r] = ld_buf(rs, vo, so[r]);
     }
   };
-  auto store_chunk = [&](int c0) {
-    float* t = &tile[0][0][0];
+  // scale / shift (the identity {1, 0} where the input has no affine) and the 16 taps of the wave's NEXT channel: fetched by scalar loads
+  // one channel ahead, so their latency sits under the current channel's FMAs
+  const float* scb = p.sc ? p.sc + n * p.C : p.ident;
+  const float* shb = p.sh ? p.sh + n * p.C : p.ident + 1;
+  const int scs = p.sc ? 1 : 0, shs = p.sh ? 1 : 0;
+  float wq[16], scq, shq;
+  auto fetch_w = [&](int j) {
+    const int c = min(chan(j), p.C - 1);
+    const float* wp = p.w + (int64_t)c * p.ws_ci;
 #pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int c = c0 + chan(i);
-      if (sdst[i] >= 0) {
-        const bool ok = soff[i] >= 0 && c < p.C;
-        const int cc = min(c, p.C - 1);
-        const float u = fmaf(pv[i], ssc[cc], ssh[cc]);
-        t[sdst[i]] = ok ? fmaxf(u, 0.f) + p.slope * fminf(u, 0.f) : 0.f;
+    for (int k = 0; k < 16; ++k) wq[k] = wp[k];
+    scq = scb[c * scs];
+    shq = shb[c * shs];
+  };
+  auto compute = [&](float (&raw)[CU][R], int round) {
+#pragma unroll
+    for (int u = 0; u < CU; ++u) {
+      const int j = round * CU + u;
+      float w[16];
+#pragma unroll
+      for (int k = 0; k < 16; ++k) w[k] = wq[k];
+      const float sc = scq, sh = shq;
+      fetch_w(j + 1);
+      if (j < nch) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const float t = fmaf(raw[u][r], sc, sh);
+          const float v0 = and_bits(fmaxf(t, 0.f) + p.slope * fminf(t, 0.f), cmask & rmask[r]);
+          const float v1 = from_next(v0), v2 = from_next(v1), v3 = from_next(v2);
+#pragma unroll
+          for (int ky = 0; ky < 4; ++ky) {
+            const int o = r - ky;
+            if (o >= 0 && o < T) {
+              acc[o] = fmaf(v0, w[ky * 4], acc[o]);
+              acc[o] = fmaf(v1, w[ky * 4 + 1], acc[o]);
+              acc[o] = fmaf(v2, w[ky * 4 + 2], acc[o]);
+              acc[o] = fmaf(v3, w[ky * 4 + 3], acc[o]);
+            }
+          }
+        }
       }
     }
-    if (tid < CK * 16) {
-      const int c = c0 + (tid >> 4);
-      wl[tid >> 4][tid & 15] = c < p.C ? p.w[(int64_t)c * p.ws_ci + (tid & 15)] : 0.f;
-    }
   };
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
-  __syncthreads();   // ssc / ssh
-  load_chunk(0);
-  store_chunk(0);
-  __syncthreads();
-  for (int c0 = 0; c0 < p.C; c0 += CK) {
-    const bool more = c0 + CK < p.C;
-    if (more) load_chunk(c0 + CK);
-#pragma unroll
-    for (int cg = 0; cg < CPG; ++cg) {
-      const int c = grp * CPG + cg;
-#pragma unroll
-      for (int ky = 0; ky < 4; ++ky) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(&tile[c][ty + ky][tx4 * 4]);
-        const f32x4 b = *reinterpret_cast<const f32x4*>(&tile[c][ty + ky][tx4 * 4 + 4]);
-        const f32x4 wv = *reinterpret_cast<const f32x4*>(&wl[c][ky * 4]);
-        const float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-#pragma unroll
-        for (int kx = 0; kx < 4; ++kx)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[j] = fmaf(v[j + kx], wv[kx], acc[j]);
-      }
-    }
-    __syncthreads();
-    if (more) {
-      store_chunk(c0 + CK);
-      __syncthreads();
-    }
+  fetch_w(0);
+  load(rawA, 0);
+  for (int i = 0; i < nround; i += 2) {
+    if (i + 1 < nround) load(rawB, i + 1);
+    compute(rawA, i);
+    if (i + 2 < nround) load(rawA, i + 2);
+    compute(rawB, i + 1);
   }
-  // partial sums of the thread groups, combined in group order (the tile memory is free after the last barrier)
-  f32x4* red = reinterpret_cast<f32x4*>(&tile[0][0][0]);
-  if (grp > 0) red[(grp - 1) * 256 + t256] = (f32x4){acc[0], acc[1], acc[2], acc[3]};
+#pragma unroll
+  for (int t = 0; t < T; ++t) red[wv][t][lane] = acc[t];
   __syncthreads();
-  if (grp > 0) return;
-#pragma unroll
-  for (int g = 1; g < NG; ++g) {
-    const f32x4 v = red[(g - 1) * 256 + t256];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] += v[j];
-  }
   const float bias = p.bias ? p.bias[0] : 0.f;
-  const int y = oy0 + ty;
-  if (y < p.OH) {
-    float* o = p.out + n * p.ons + (int64_t)y * p.OW;
+  const int x = ox0 + lane;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int x = ox0 + tx4 * 4 + j;
-      if (x < p.OW) o[x] = acc[j] + bias;
-    }
+  for (int j = 0; j < T / 4; ++j) {
+    const int t = wv * (T / 4) + j, y = oy0 + t;
+    const float s = ((red[0][t][lane] + red[1][t][lane]) + red[2][t][lane]) + red[3][t][lane];
+    if (lane < HK_VL && x < p.OW && y < p.OH) p.out[n * p.ons + (int64_t)y * p.OW + x] = s + bias;
   }
 }
 
@@ -264,10 +270,10 @@ int vts_conv_head_try(const vts_conv_desc* d, hipStream_t st) {
   k.IH = d->IH; k.IW = d->IW; k.OH = d->OH; k.OW = d->OW; k.pad = d->pad; k.padx = d->pad + d->pad_dx;
   k.w = d->w; k.ws_ci = d->ws_ci; k.bias = d->bias; k.out = d->out; k.ons = d->out_nstride;
   k.slope = vts_slope(d->act_in);
-  k.ident = nullptr;
-  dim3 grid(cdiv(d->OW, HK_TX), cdiv(d->OH, HK_TY), d->N);
-  hipLaunchKernelGGL((conv_head_kernel<8>), grid, dim3(1024), 0, st, k);
-  vts_set_kernel("conv_head_kernel<8>");
+  k.ident = vts_ident();
+  dim3 grid(cdiv(d->OW, HK_VL), cdiv(d->OH, HK_T), d->N);
+  hipLaunchKernelGGL((conv_head_kernel<HK_T, HK_CU>), grid, dim3(256), 0, st, k);
+  vts_set_kernel("conv_head_kernel<%d, %d>", HK_T, HK_CU);
   VTS_CHECK_LAUNCH("vts_conv4x4 (head)");
   return VTS_OK;
 }

@@ -837,8 +837,7 @@ __global__ __launch_bounds__(256) void wgrad_head_kernel(const HeadWK p) {
   const int rg = tid & 3, ky = (tid >> 2) & 3, chl = tid >> 4;
   const int64_t hplane = (int64_t)p.HH * p.HW;
   float* part = p.part + (int64_t)tile * p.CH * 16;
-  // Software pipeline over the 16-channel chunks: the raw loads of chunk k + 1 are issued before the multiply phase of chunk k and
-  // finished (affine, activation, padding -> LDS) after it.  Row-wise staging: wave w takes channels w, w + 4, ... of the chunk, one
+  // Row-wise staging: wave w takes channels w, w + 4, ... of the chunk, one
   // patch row per wave instruction (lanes = columns), so channel, row, bounds and the channel's scale / shift are wave-uniform
   // (the element-wise form spent ~45 instructions per loaded value); all 76 loads of a chunk are in flight together.
   const int lane = tid & 63;
@@ -873,11 +872,16 @@ __global__ __launch_bounds__(256) void wgrad_head_kernel(const HeadWK p) {
       }
     }
   };
-  load_chunk(0);
-  for (int c0 = 0; c0 < p.CH; c0 += HWG_CK) {
-    __syncthreads();                      // the previous chunk's readers are done (first pass: the lo tile is complete)
+  // One 16-channel chunk per workgroup (blockIdx.y; round 13): until then a workgroup walked the chunks of its tile one after the other --
+  // four serial load -> LDS -> barrier -> FMA phases at 64 channels, 24 - 36 us whatever the map (a 131^2 map of 8 images has 360
+  // tiles: ~1.4 workgroups per CU, so the time was one workgroup's chain).  The chunks are independent (a thread owns (channel, ky)),
+  // so each is its own workgroup now: a quarter of the chain, four times the workgroups, every result bit for bit the same
+  // (8 images, with the reduction: 34^2 23.8 -> 11.5 us, 66^2 26.3 -> 16.1, 130^2 42.1 -> 39.3; tools/mb_heads.py, same box).
+  {
+    const int c0 = blockIdx.y * HWG_CK;
+    load_chunk(c0);
+    __syncthreads();                      // the lo tile is complete
     store_chunk(c0);
-    if (c0 + HWG_CK < p.CH) load_chunk(c0 + HWG_CK);
     __syncthreads();
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -936,7 +940,7 @@ constexpr int RB_JOBS = 40;
 struct ReduceTable {
   int njobs;
   int blk_start[RB_JOBS + 1];
-  unsigned char narrow[RB_JOBS];   // 1: 64 elements per workgroup, the lanes of a wave also split the copies (many copies of a small dw)
+  unsigned char narrow[RB_JOBS];   // 1: 64 elements per workgroup, the lanes of a wave also split the copies (many copies of a small dw); 2..5: few-copy form (reduce_few)
   vts_reduce_job job[RB_JOBS];
 };
 
@@ -947,6 +951,76 @@ struct ReduceTable {
 // loads is what bounds them), and everything is combined in a fixed order: pairwise over a0..a7 per wave, then waves 0..15.
 // Deterministic, no float atomics.
 constexpr int RB_ELEMS = 256;
+
+// Few-copy form (jobs of at most 32 copies: the inner U-Net layers, whose dw has 0.1 .. 0.8 M elements in 4 .. 32 copies).  In the
+// 256-element form above a workgroup of such a job moves 4 .. 32 KB, most of its sixteen waves load nothing, and it lives one memory
+// round trip plus a barrier and a 16-wave LDS combine: thousands of such workgroups bound the flush, not HBM.  Here every WAVE owns
+// its own 256-element block (a workgroup owns 4096 elements), walks all copies of it with eight 16-byte loads in flight per lane, and
+// needs neither LDS nor a barrier.  The arithmetic per element is exactly that of the 256-element form, so dw is bit-identical:
+// "virtual wave" w = 0..15 sums copies w + 16 u into a[u] (a job of this form has at most 16 * NU copies, so u < NU and a copy count
+// beyond 128 never occurs: one term per a[u], from +0), the segment sum is ((a0+a1)+(a2+a3))+((a4+a5)+(a6+a7)) with the
+// absent a[u] = +0, segments are added in order into s_w (from +0), and the result is s_0 + s_1 + ... + s_15, left to right.
+// NW: virtual waves that can hold a copy (the others contribute their +0 all the same); loads are unconditional on a clamped copy index.
+// Measured (tools/mb_heads.py, the ten jobs of the generator backward's first flush, 116 MB, 4 .. 102 copies): 53.6 -> 25.9 us; its
+// 4-copy job of 0.76 M elements alone 14.1 -> 4.3 us.
+constexpr int RB_FEW_ELEMS = 16 * RB_ELEMS;
+template <int NU, int NW>
+__device__ __forceinline__ void reduce_few(const vts_reduce_job& j, int64_t base, int lane) {
+  constexpr int WU = (8 / NU) < NW ? (8 / NU) : NW;   // virtual waves per batch of loads
+  const bool tail = base + RB_ELEMS > j.nel;
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  f32x4 total = zero;
+#pragma unroll
+  for (int w0 = 0; w0 < 16; w0 += WU) {
+    f32x4 s[WU];
+#pragma unroll
+    for (int i = 0; i < WU; ++i) s[i] = zero;
+    for (int sg = 0; sg < j.nseg; ++sg) {
+      const float* part = j.part[sg];
+      const int pw = j.pw[sg];
+      const bool vec = !tail && (j.nel & 3) == 0 && (reinterpret_cast<uintptr_t>(part) & 15) == 0;
+      f32x4 a[WU][NU];
+#pragma unroll
+      for (int i = 0; i < WU; ++i)
+#pragma unroll
+        for (int u = 0; u < NU; ++u) a[i][u] = zero;
+      if (w0 < NW && w0 < pw) {
+        f32x4 v[WU][NU];
+#pragma unroll
+        for (int i = 0; i < WU; ++i)
+#pragma unroll
+          for (int u = 0; u < NU; ++u) {
+            const int kk = min(w0 + i + 16 * u, pw - 1);
+            const float* row = part + (int64_t)kk * j.nel + base;
+            if (vec) {
+              v[i][u] = *reinterpret_cast<const f32x4*>(row + lane * 4);
+            } else {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) v[i][u][e] = row[min((int64_t)(lane * 4 + e), j.nel - 1 - base)];
+            }
+          }
+#pragma unroll
+        for (int i = 0; i < WU; ++i)
+#pragma unroll
+          for (int u = 0; u < NU; ++u)
+            if (w0 + i + 16 * u < pw) a[i][u] += v[i][u];
+      }
+#pragma unroll
+      for (int i = 0; i < WU; ++i) {
+        auto A = [&](int u) { return u < NU ? a[i][u] : zero; };
+        s[i] += ((A(0) + A(1)) + (A(2) + A(3))) + ((A(4) + A(5)) + (A(6) + A(7)));
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < WU; ++i) total = (w0 + i == 0) ? s[0] : total + s[i];
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int64_t i = base + lane * 4 + e;
+    if (i < j.nel) j.dw[i] = j.accumulate ? j.dw[i] + total[e] : total[e];
+  }
+}
+
 __global__ __launch_bounds__(1024) void wgrad_reduce_batch_kernel(const ReduceTable t) {
   __shared__ f32x4 red[16][64];
   int lo = 0, hi = t.njobs - 1;   // uniform binary search: last job with blk_start <= blockIdx.x
@@ -957,6 +1031,15 @@ __global__ __launch_bounds__(1024) void wgrad_reduce_batch_kernel(const ReduceTa
   }
   const vts_reduce_job& j = t.job[lo];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (t.narrow[lo] >= 2) {
+    const int64_t base = (int64_t)(blockIdx.x - t.blk_start[lo]) * RB_FEW_ELEMS + __builtin_amdgcn_readfirstlane(w) * RB_ELEMS;
+    if (base >= j.nel) return;
+    if (t.narrow[lo] == 2) reduce_few<1, 4>(j, base, lane);
+    else if (t.narrow[lo] == 3) reduce_few<1, 8>(j, base, lane);
+    else if (t.narrow[lo] == 4) reduce_few<1, 16>(j, base, lane);
+    else reduce_few<2, 16>(j, base, lane);
+    return;
+  }
   if (t.narrow[lo]) {
     // Thin layers have 500 .. 1500 copies of a few thousand elements: with 256 elements per workgroup six workgroups would each walk
     // ~100 copies per wave (a chain of a dozen dependent load rounds).  Here a workgroup owns 64 elements, 16 lanes x 16 bytes, and
@@ -1350,7 +1433,7 @@ extern "C" int vts_wgrad4x4(const vts_wgrad_desc* d, float* ws, void* stream) {
     q.hi_slope = vts_slope(d->act_hi);
     q.tiles_y = pl.tiles_y; q.tiles_x = pl.tiles_x;
     q.part = ws;
-    hipLaunchKernelGGL(wgrad_head_kernel, dim3(pl.ntiles), dim3(256), 0, st, q);
+    hipLaunchKernelGGL(wgrad_head_kernel, dim3(pl.ntiles, cdiv(q.CH, HWG_CK)), dim3(256), 0, st, q);
     vts_set_kernel("wgrad_head_kernel");
     VTS_CHECK_LAUNCH("vts_wgrad4x4 (single channel)");
     if (d->defer) return VTS_OK;
@@ -1399,7 +1482,8 @@ extern "C" int vts_wgrad_reduce_batch(const vts_reduce_job* jobs, int njobs, voi
       for (int sg = 0; sg < q.nseg; ++sg) maxpw = q.pw[sg] > maxpw ? q.pw[sg] : maxpw;
       constexpr int narrow_min = 256;                // (lane groups split the copies above it: step 6.47 -> 6.36 ms, round 3)
       t.narrow[j] = maxpw > narrow_min ? 1 : 0;      // more than 16 copies per wave of the 256-element form
-      blocks += (int)cdiv64(q.nel, t.narrow[j] ? 64 : RB_ELEMS);
+      if (maxpw <= 32) t.narrow[j] = maxpw <= 4 ? 2 : maxpw <= 8 ? 3 : maxpw <= 16 ? 4 : 5;   // few copies: a wave per 256-element block
+      blocks += (int)cdiv64(q.nel, t.narrow[j] >= 2 ? RB_FEW_ELEMS : t.narrow[j] ? 64 : RB_ELEMS);
     }
     t.blk_start[t.njobs] = blocks;
     hipLaunchKernelGGL(wgrad_reduce_batch_kernel, dim3((unsigned)blocks), dim3(1024), 0, st, t);

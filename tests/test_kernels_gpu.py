@@ -936,6 +936,64 @@ def test_deferred_weight_gradient_reduction_equals_immediate(shape):
     assert rel(got, ref) < 2e-6
 
 
+def test_deferred_weight_gradients_of_two_lanes_eager_and_captured():
+    """Two lanes of engine._run_lanes inside one deferred_wgrad(), each with two contributions (the second accumulating) to a dw of
+    its own: every lane reduces its partials on its own stream, from its own arena.  Against the immediate reduction; then the same
+    block captured as a graph and replayed twice over changed inputs -- the arenas hand out the same addresses after every flush, so
+    the captured addresses stay the ones the replays write -- with the scratch buffer of the launch lane untouched throughout."""
+    from vts import engine, ops
+
+    dev = _dev()
+    shapes = [(2, 3, 97, 5), (4, 10, 200, 9)]            # ragged rows (the two smallest shapes of the test above), one per lane
+    bufs = []
+    for k, (n, cl, lh, ch) in enumerate(shapes):
+        hh = (lh - 1) * 2 + 4 - 2
+        bufs.append([detrand.uniform((n, cl, lh, lh), 5, "lo%d" % k).to(dev), detrand.uniform((n, ch, hh, hh), 5, "hi%d" % k).to(dev),
+                     detrand.uniform((n, cl, lh, lh), 5, "lo2%d" % k).to(dev)])
+    got = [torch.full((cl, ch, 4, 4), 7.0, device=dev) for _, cl, _, ch in shapes]
+    ref = [torch.empty_like(g) for g in got]
+
+    def lane(k, dw, defer):
+        lo, hi, lo2 = bufs[k]
+        ops.wgrad4x4(lo, hi, dw[k], stride=2, pad=1, defer=defer)
+        ops.wgrad4x4(lo2, hi, dw[k], stride=2, pad=1, defer=defer, accumulate=True)
+
+    def immediate():
+        for k in range(len(shapes)):
+            lane(k, ref, False)
+
+    def block():
+        with ops.deferred_wgrad():
+            engine._run_lanes(len(shapes), lambda k: lane(k, got, None))
+
+    immediate()
+    ws = ops.workspace(1, dev)
+    block()
+    for g, r in zip(got, ref):
+        assert rel(g, r) < 2e-6
+    torch.cuda.synchronize()
+    ops.freeze_ws("two-lane test")
+    try:
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=torch.cuda.Stream(), capture_error_mode="thread_local"):
+            block()
+        for shift in (1, 2):
+            for lo, hi, lo2 in bufs:
+                lo.copy_(torch.roll(lo, shift, 2))       # other rows of lo meet each row of hi: a different gradient, not a multiple
+                hi.mul_(-0.5)
+            for g in got:
+                g.fill_(7.0)
+            immediate()
+            graph.replay()
+            for g, r in zip(got, ref):
+                assert rel(g, r) < 2e-6
+        torch.cuda.synchronize()
+        del graph
+    finally:
+        ops.release_ws("two-lane test")
+    assert ops.workspace(1, dev) is ws
+
+
 @pytest.mark.parametrize("shape", [(2, 64, 35, 35, 2, True), (3, 20, 67, 40, 2, True), (2, 5, 16, 33, 1, False), (8, 64, 131, 131, 2, True)])
 def test_single_channel_weight_gradient(shape):
     """the PatchGAN head's weight gradient (one low-resolution channel) on the vector-ALU member (wgrad_head_kernel) against

@@ -946,10 +946,9 @@ class SinSKITGModel(BaseModel):
 
             def d2_update(scales):
                 def run():
-                    with ops.deferred_wgrad():
+                    with ops.deferred_wgrad():      # (ends on this lane: its partials are reduced here, on the lane's stream)
                         for sc in scales:
                             engine._scale_lane(D2, sc, upd, self.criterionGAN, knocked_out=(chain_d2["index0"] + sc) in engine.KO_LANES)
-                        ops.wgrad_flush(ops.WS_LANE)
                 return run
             lanes = []
             try:

@@ -19,6 +19,7 @@ from . import tune
 
 import torch
 
+from . import lanes
 from . import lib as L
 from . import ops
 from .ops import Act
@@ -222,12 +223,7 @@ def unet_forward_infer(G, x, style_code=None, style_tiles=None):
             x0 = _as_act(x[0] if isinstance(x, (tuple, list)) else x).data
             hh, ww = x0.shape[2] >> G.num_downs, x0.shape[3] >> G.num_downs
             tile = style_code.to(torch.float32)[:, :, None, None].expand(-1, -1, hh, ww).contiguous()
-    side = None
-    if PARALLEL_SCALES and G.num_layer_separate > 0:
-        pool = _SIDE_STREAMS.setdefault(torch.cuda.current_device(), [])
-        if not pool:
-            pool.append(torch.cuda.Stream())
-        side = pool[0]
+    side = lanes.lane(1).stream if PARALLEL_SCALES and G.num_layer_separate > 0 else None
     return unet_forward_c(G, x, style_tile=tile, side_stream=side)
 
 
@@ -952,9 +948,6 @@ def _pool_act(a):
 # tactile patches never fill 256 CUs): they run concurrently on side HIP streams, forked from and joined back
 # into the launch stream (so the schedule is still a DAG that torch.cuda.CUDAGraph captures as such).
 PARALLEL_SCALES = tune.get("VTS_PARALLEL_SCALES", "1") != "0"
-_SIDE_STREAMS = {}
-
-
 SIDE_QUEUES = 2     # round 4: one -> two 5.65 -> 5.59 ms (three: 5.61); round 6, chained schedule: one / three + 0.04 / + 0.05 ms
 
 
@@ -968,13 +961,8 @@ class SideQueue:
     LANE = 7
 
     def __init__(self):
-        self.main = torch.cuda.current_stream()
-        side = _SIDE_STREAMS.setdefault(torch.cuda.current_device(), [])
-        while len(side) < SideQueue.LANE:
-            side.append(torch.cuda.Stream())
-        # items alternate between two streams (scratch / partial-arena index = the stream's lane number)
-        self.lanes = [SideQueue.LANE - k for k in range(SIDE_QUEUES)]
-        self.streams = [side[ln - 1] for ln in self.lanes]
+        # items alternate between two lanes of fixed number, reserved: no other fork may grow into them
+        self.fork = lanes.Fork(reserve=[SideQueue.LANE - k for k in range(SIDE_QUEUES)])
         self.turn = 0
         self.keep = []
         self.on = PARALLEL_SCALES
@@ -982,33 +970,24 @@ class SideQueue:
     def run(self, fn, *tensors):
         if not self.on:
             return fn()
-        k = self.turn % len(self.lanes)
+        k = self.turn % len(self.fork.lanes)
         self.turn += 1
-        stream, ln = self.streams[k], self.lanes[k]
-        stream.wait_stream(self.main)
-        lane, ops.WS_LANE = ops.WS_LANE, ln
+        self.fork.fork(k)
         try:
-            with torch.cuda.stream(stream):
+            with self.fork.on(k):
                 fn()
         except BaseException:
-            ops.WS_LANE = lane
             ops.wgrad_discard()
-            for st in self.streams:
-                self.main.wait_stream(st)
+            self.fork.join()
             raise
-        ops.WS_LANE = lane
         self.keep.extend(tensors)
 
     def join(self):
         if self.on:
-            lane = ops.WS_LANE
-            for stream, ln in zip(self.streams, self.lanes):
-                ops.WS_LANE = ln
-                with torch.cuda.stream(stream):
-                    ops.wgrad_flush(ln)     # this queue's deferred weight-gradient reduction, on its own stream
-            ops.WS_LANE = lane
-            for stream in self.streams:
-                self.main.wait_stream(stream)
+            for k in range(len(self.fork.lanes)):
+                with self.fork.on(k):
+                    ops.wgrad_flush()       # this queue's deferred weight-gradient reduction, on its own stream
+            self.fork.join()
         self.keep = []
 
 
@@ -1023,42 +1002,20 @@ def _run_lanes(n_lanes, body):
             body(lane)
         return
     # A call made from the launch-stream lane of an enclosing call (the generator forward's two decoder lanes inside the lane set of
-    # _msd_multi(extra_main=True)) takes the side streams / scratch indices BEHIND the enclosing call's: `_LANE_BASE`.  (From a SIDE lane
+    # _msd_multi(extra_main=True)) takes the lanes BEHIND the enclosing call's: the fork holds them while body(0) runs.  (From a SIDE lane
     # a fork is still forbidden: hipStreamEndCapture does not survive it.)
-    global _LANE_BASE
-    base = _LANE_BASE
-    main = torch.cuda.current_stream()
-    dev = torch.cuda.current_device()
-    side = _SIDE_STREAMS.setdefault(dev, [])
-    while len(side) < base + n_lanes - 1:
-        side.append(torch.cuda.Stream())
-    mine = side[base:base + n_lanes - 1]
-    for st in mine:
-        st.wait_stream(main)
-    ws0 = ops.WS_LANE
-    try:
+    with lanes.Fork(n_lanes - 1) as f:      # a lane body raised: no stale partial jobs for the next backward, no dangling fork
+        f.fork()
         for lane in range(1, n_lanes):
-            ops.WS_LANE = base + lane
-            with torch.cuda.stream(mine[lane - 1]):
+            with f.on(lane - 1):
                 body(lane)
-                ops.wgrad_flush(base + lane)       # deferred weight-gradient reductions of this lane, on its own stream
-        ops.WS_LANE = ws0
-        _LANE_BASE = base + n_lanes - 1
+                ops.wgrad_flush()           # deferred weight-gradient reductions of this lane, on its own stream
+        f.hold()
         try:
             body(0)
         finally:
-            _LANE_BASE = base
-        ops.wgrad_flush(ws0)
-    except BaseException:
-        ops.WS_LANE = ws0
-        ops.wgrad_discard()                 # a lane body raised: no stale partial jobs for the next backward
-        raise
-    finally:
-        for st in mine:                     # the side streams are joined back in every case (a capture must not end with a dangling fork)
-            main.wait_stream(st)
-
-
-_LANE_BASE = 0
+            f.release()
+        ops.wgrad_flush()
 
 
 def fork_lane(fn):
@@ -1066,39 +1023,25 @@ def fork_lane(fn):
     join, lane calls made on the launch stream (_run_lanes, msd_chain) take the side streams BEHIND this one -- the lane may stay open
     across several of them (the D2 chain of the training step runs beside the D1 chain AND the generator's backward).  fn must not
     fork lanes itself (no fork from a side stream: hipStreamEndCapture does not survive one).  Serial schedule: fn() runs inline."""
-    global _LANE_BASE
     if not PARALLEL_SCALES:
         fn()
         return None
-    base = _LANE_BASE
-    main = torch.cuda.current_stream()
-    side = _SIDE_STREAMS.setdefault(torch.cuda.current_device(), [])
-    while len(side) < base + 1:
-        side.append(torch.cuda.Stream())
-    st = side[base]
-    st.wait_stream(main)
-    ws0, ops.WS_LANE = ops.WS_LANE, base + 1
-    _LANE_BASE = base + 1
+    f = lanes.Fork(1)
+    f.fork()
+    f.hold()
     try:
-        with torch.cuda.stream(st):
+        with f.on(0):
             fn()
     except BaseException:
-        _LANE_BASE = base
-        main.wait_stream(st)
+        f.close()
         raise
-    finally:
-        ops.WS_LANE = ws0
-    return (st, base)
+    return f
 
 
 def join_lane(handle):
     """the current stream waits for the lane fork_lane opened; its side stream is free for other lanes again"""
-    global _LANE_BASE
-    if handle is None:
-        return
-    st, base = handle
-    torch.cuda.current_stream().wait_stream(st)
-    _LANE_BASE = base
+    if handle is not None:
+        handle.close(torch.cuda.current_stream())
 
 
 def _pyramid(D, in0, in1):
@@ -1683,7 +1626,7 @@ def _msd_multi(jobs, criterion, extra=None, extra_cost=0.1, extra_main=False, st
 
     nograd = all(not p.get("param_grads", True) for _, passes in jobs for p in passes)     # the generator step's passes
     groups = _lane_groups(costs, "VTS_LANE_GROUPS_G" if nograd else "VTS_LANE_GROUPS", streams)
-    with ops.deferred_wgrad():    # one reduction launch for the weight-gradient partials of all lanes, after they have joined
+    with ops.deferred_wgrad():    # (_run_lanes reduces the weight-gradient partials of each lane on the lane's own stream)
         _run_lanes(len(groups), lambda gi: [lane(i) for i in groups[gi]])
     _finish_passes(jobs)
 
@@ -1706,7 +1649,6 @@ def msd_chain(chain, criterion, side=None, side_cost=0.1, serial=False):
     chain: dict(D=, index0=<lane number of scale 0, for VTS_KO_LANES>, update=[passes], mid=callable, gstep=callable -> [passes])
     (pass dictionaries as for msd_multi).  side: callable that runs as one more lane inside the chain's stream pair and is complete before
     `mid` (the generator's L1 terms: the D1 pass of the generator step accumulates onto their gradient)."""
-    global _LANE_BASE
     D = chain["D"]
     _prepare_passes([(D, chain["update"])])
 
@@ -1731,7 +1673,7 @@ def msd_chain(chain, criterion, side=None, side_cost=0.1, serial=False):
                 body()
             if side is not None:
                 side()
-            ops.wgrad_flush(ops.WS_LANE)
+            ops.wgrad_flush()            # in front of `mid`, the optimiser step (the context's exit would reduce too late)
             _finish_passes([(D, chain["update"])])
             chain["mid"]()
             g = chain["gstep"]()
@@ -1741,53 +1683,35 @@ def msd_chain(chain, criterion, side=None, side_cost=0.1, serial=False):
             _finish_passes([(D, g)])
         return
 
-    base = _LANE_BASE
-    main = torch.cuda.current_stream()
-    side_streams = _SIDE_STREAMS.setdefault(torch.cuda.current_device(), [])
-    while len(side_streams) < base + 1:
-        side_streams.append(torch.cuda.Stream())
-    second = side_streams[base]
-    ws0 = ops.WS_LANE
-
-    def on_second(fn):
-        ops.WS_LANE = base + 1
-        try:
-            with torch.cuda.stream(second):
-                fn()
-        finally:
-            ops.WS_LANE = ws0
-
-    _LANE_BASE = base + 1
-    try:
+    with lanes.Fork(1) as f:      # (also on an exception: no stale partial jobs, the base rewound, the second stream joined)
+        f.hold()
         with ops.deferred_wgrad():
-            second.wait_stream(main)
+            f.fork()
             items = stage_lanes(chain["update"])
             if side is not None:
                 items.append((float(side_cost), side))
             b_main, b_second = split2(items)
-            on_second(lambda: ([b() for b in b_second], ops.wgrad_flush(base + 1)))
+            with f.on(0):
+                for b in b_second:
+                    b()
+                ops.wgrad_flush()
             for b in b_main:
                 b()
-            ops.wgrad_flush(ws0)
-            main.wait_stream(second)                  # the chain's own join, its optimiser step
+            ops.wgrad_flush()
+            f.join()                                  # the chain's own join, its optimiser step
             _finish_passes([(D, chain["update"])])
             chain["mid"]()
             g = chain["gstep"]()
             _prepare_passes([(D, g)])
-            second.wait_stream(main)
+            f.fork()
             b_main, b_second = split2(stage_lanes(g))
-            on_second(lambda: [b() for b in b_second])
+            with f.on(0):
+                for b in b_second:
+                    b()
             for b in b_main:
                 b()
-            main.wait_stream(second)
+            f.join()
             _finish_passes([(D, g)])
-    except BaseException:
-        ops.WS_LANE = ws0
-        ops.wgrad_discard()
-        raise
-    finally:
-        _LANE_BASE = base
-        main.wait_stream(second)                # joined back in every case (a capture must not end with a dangling fork)
 
 
 # ======================================================================================================================

@@ -10,6 +10,7 @@ from . import tune
 
 import torch
 
+from . import lanes
 from . import lib as L
 
 
@@ -62,28 +63,11 @@ def _run(label, nbytes, flops, fn, *args):
     DETAIL = None
 
 
-def _numel(op):
-    return 0
-
-
-_ws = {}
-
-
 def workspace(nfloats, device):
-    """Grow-only scratch; safe to share because every kernel runs in stream order."""
-    key = (str(device), WS_LANE)   # one scratch per concurrent lane (engine._run_lanes / SideQueue)
-    t = _ws.get(key)
-    if t is None or t.numel() < nfloats:
-        if t is not None and frozen_ws():
-            _retired.append(t)   # captured HIP graphs hold the old pointer: keep that buffer alive, never reuse it
-        t = torch.empty(max(int(nfloats), 2 * (t.numel() if t is not None else 0), 1 << 20), dtype=torch.float32, device=device)
-        _ws[key] = t
-    return t
+    """Grow-only scratch of the current lane; safe to share within it because every kernel runs in stream order."""
+    return lanes.current(device).workspace(nfloats, frozen_ws())
 
 
-_retired = []
-
-_counters = {}
 # Off by default: measured 3x SLOWER on MI355X (10.5 -> 30 ms per step).  The release / acquire fences the pattern needs are
 # device-scope, and with one L2 per XCD a device-scope fence writes back / invalidates that whole L2 -- thousands of workgroups doing
 # so while six other lanes keep the L2s dirty is far more expensive than the ~140 tiny finalize launches it saves.  A kernel boundary
@@ -94,13 +78,7 @@ FUSE_FINALIZE = tune.get("VTS_FUSE_FINALIZE", "0") == "1"
 def counters(device):
     """zeroed int32 scratch of the current lane for the 'last workgroup finalises' kernels (they leave it zero); None switches
     the library back to its separate finalize launches"""
-    if not FUSE_FINALIZE:
-        return None
-    key = (str(device), WS_LANE)
-    t = _counters.get(key)
-    if t is None:
-        t = _counters[key] = torch.zeros(1 << 16, dtype=torch.int32, device=device)
-    return t
+    return lanes.current(device).counters() if FUSE_FINALIZE else None
 
 
 # The workspace is frozen (a grown buffer is retired, never freed) while any captured HIP graph that holds its pointer is alive.
@@ -121,9 +99,6 @@ def frozen_ws():
     return bool(_WS_HOLDERS)
 
 
-WS_LANE = 0        # which scratch buffer the wrappers use: 0 = the launch stream, i = side lane i (engine._run_lanes)
-
-
 def _op(a):
     if a is None:
         return L.Operand(None, None, None, 0, 0)
@@ -136,20 +111,13 @@ def _op(a):
 
 BWD_SUMS = tune.get("VTS_BWD_SUMS", "1") != "0"
 BSUMS = {}       # data_ptr of a gradient tensor -> (partials, slots, the tensor): sums its producing convolution left for norm_bwd
-
-_stat_ws = {}
+lanes.on_discard(BSUMS.clear)      # (an abandoned backward never runs that norm_bwd)
 
 
 def stat_workspace(nfloats, device):
     """scratch for the epilogue statistics partials of vts_conv4x4_norm: one per lane, separate from `workspace` (the k-split
     partials of the same call live there)"""
-    key = (str(device), WS_LANE)
-    t = _stat_ws.get(key)
-    if t is None or t.numel() < nfloats:
-        if t is not None and frozen_ws():
-            _retired.append(t)
-        t = _stat_ws[key] = torch.empty(max(int(nfloats), 2 * (t.numel() if t is not None else 0), 1 << 18), dtype=torch.float32, device=device)
-    return t
+    return lanes.current(device).stat_workspace(nfloats, frozen_ws())
 
 
 def conv4x4(in0, w, ws_co, ws_ci, cout, out, *, in1=None, bias=None, stride=2, pad=1, transposed=False, act_in=0,
@@ -231,50 +199,10 @@ def conv4x4(in0, w, ws_co, ws_ci, cout, out, *, in1=None, bias=None, stride=2, p
 
 
 # ---- deferred weight-gradient reduction -------------------------------------------------------------------------------
-# Inside `with deferred_wgrad():` every wgrad4x4 leaves its per-workgroup partials in a per-lane arena and the deterministic
-# reduction of ALL of them is one vts_wgrad_reduce_batch launch when the outermost context exits (the engine exits it after
-# its side streams have joined the launch stream).  Outside the context wgrad4x4 reduces immediately.
-_DEFER_DEPTH = 0
-_pending = []        # ReduceJob-like dicts, in enqueue order
-_pending_by_dw = {}
-_arenas = {}
-
-
-class _Arena:
-    """bump allocator over grow-only blocks; the allocation sequence of a training step is the same every step, so a reset
-    at every flush hands out the same addresses again (captured HIP graphs stay valid; blocks are never freed)"""
-
-    def __init__(self, device):
-        self.device, self.blocks, self.cur, self.off = device, [], 0, 0
-
-    def alloc(self, nfloats):
-        nfloats = (int(nfloats) + 63) // 64 * 64
-        while True:
-            if self.cur < len(self.blocks):
-                b = self.blocks[self.cur]
-                if self.off + nfloats <= b.numel():
-                    t = b[self.off:self.off + nfloats]
-                    self.off += nfloats
-                    return t
-                if self.off == 0:      # an empty block that is too small: replace it by a larger one (the old one stays alive)
-                    _retired.append(b)
-                    self.blocks[self.cur] = torch.empty(max(nfloats, 2 * b.numel()), dtype=torch.float32, device=self.device)
-                    continue
-                self.cur, self.off = self.cur + 1, 0
-            else:
-                self.blocks.append(torch.empty(max(nfloats, 16 << 20), dtype=torch.float32, device=self.device))
-
-    def reset(self):
-        self.cur, self.off = 0, 0
-
-
-def _arena(device):
-    key = (str(device), WS_LANE)
-    a = _arenas.get(key)
-    if a is None:
-        a = _arenas[key] = _Arena(device)
-    return a
-
+# Inside `with deferred_wgrad():` every wgrad4x4 leaves its per-workgroup partials in the arena of its lane, and each lane reduces its
+# own, deterministically, by one vts_wgrad_reduce_batch launch on its own stream: when FLUSH_BYTES are pending, when the schedule
+# flushes the lane (engine._run_lanes, SideQueue.join, msd_chain), and when the outermost context exits on it.  Outside the context
+# wgrad4x4 reduces immediately.
 
 # a lane reduces its pending partials once they exceed this (keeps the reduction spread over the backward; 32 / 256 / 4096 MB: within
 # 0.03 ms.  Reducing every weight gradient right behind its launch instead of deferring: + 0.22 ms per step, round 6)
@@ -282,10 +210,10 @@ FLUSH_BYTES = 96 << 20
 
 
 def wgrad_flush(lane=None):
-    """Reduce pending weight-gradient partials on the CURRENT stream: those of one lane (the caller is on that lane's stream, or
-    has joined it), or of every lane (lane None: call on the launch stream after all lanes have joined)."""
-    global _pending
-    todo = [q for q in _pending if lane is None or q["lane"] == lane]
+    """Reduce the pending weight-gradient partials of one lane (None: the current one) on the CURRENT stream: the caller is on that
+    lane's stream, or has joined it."""
+    ln = lanes.current() if lane is None else lanes.lane(lane)
+    todo = ln.pending
     if not todo:
         return
     jobs = (L.ReduceJob * len(todo))()
@@ -295,46 +223,40 @@ def wgrad_flush(lane=None):
         for i, (part, pw) in enumerate(q["segs"]):
             j.part[i], j.pw[i] = part.data_ptr(), pw
             nbytes += 4.0 * pw * q["nel"]
-        _pending_by_dw.pop(q["dw"].data_ptr(), None)
     if TIMER is not None:
         global DETAIL
         DETAIL = "%d jobs %.1f MB partials, copies per job %d..%d" % (len(todo), nbytes / 1e6, min(pw for q in todo for _, pw in q["segs"]),
                                                                      max(pw for q in todo for _, pw in q["segs"]))
     _run("wgrad_reduce_batch", nbytes, 0.0, L.load().vts_wgrad_reduce_batch, jobs, len(todo), L.stream())
-    _pending = [q for q in _pending if not (lane is None or q["lane"] == lane)]
-    for (dev, ln), a in _arenas.items():
-        if lane is None or ln == lane:
-            a.reset()
+    ln.clear()
 
 
 def wgrad_discard():
     """drop every pending partial job and rewind the arenas (exceptional exit of a backward: nothing is reduced)"""
-    global _pending
-    _pending = []
-    _pending_by_dw.clear()
-    BSUMS.clear()
-    for a in _arenas.values():
-        a.reset()
+    lanes.discard()
 
 
 def wgrad_pending_bytes(lane):
-    return sum(4.0 * pw * q["nel"] for q in _pending if q["lane"] == lane for _, pw in q["segs"])
+    return lanes.lane(lane).pending_bytes()
 
 
 class deferred_wgrad:
     def __enter__(self):
-        global _DEFER_DEPTH
-        _DEFER_DEPTH += 1
+        lanes.defer(+1)
         return self
 
     def __exit__(self, exc_type, exc, tb):
-        global _DEFER_DEPTH
-        _DEFER_DEPTH -= 1
-        if _DEFER_DEPTH == 0:
-            if exc_type is None:
-                wgrad_flush()
+        if lanes.defer(-1) == 0:
+            mine = lanes.current().index
+            foreign = [n for n in lanes.pending_lanes() if n != mine]
+            if exc_type is None and not foreign:
+                wgrad_flush()       # this lane's own partials, on its own stream
             else:
                 wgrad_discard()     # a failed backward must not leave stale partial jobs for the next one to reduce
+                if exc_type is None:
+                    # another lane's partials are reduced on that lane's stream, or behind a join with it: neither holds here
+                    raise RuntimeError("deferred_wgrad ends on lane %d while lane %s still holds unreduced partials: flush a lane "
+                                       "on its own stream before the context ends" % (mine, ", ".join(map(str, foreign))))
         return False
 
 
@@ -355,11 +277,12 @@ def wgrad4x4(lo0, hi0, dw, *, lo1=None, hi1=None, act_lo=0, act_hi=0, stride=2, 
     cl, chn = d.lo0.C + d.lo1.C, d.hi0.C + d.hi1.C
     nel = cl * chn * 16
     if defer is None:
-        defer = _DEFER_DEPTH > 0
-    prev = _pending_by_dw.get(dw.data_ptr()) if defer else None
+        defer = lanes.defer() > 0
+    ln = lanes.current(lo.device)
+    prev = ln.by_dw.get(dw.data_ptr()) if defer else None
     if prev is not None and (len(prev["segs"]) >= 4 or prev["nel"] != nel):
         raise RuntimeError("wgrad4x4: more than 4 deferred contributions to one weight gradient")
-    ws = _arena(lo.device).alloc(n) if defer else workspace(n, lo.device)
+    ws = ln.arena.alloc(n) if defer else workspace(n, lo.device)
     d.defer = int(bool(defer))
     flops = 2.0 * d.N * d.LH * d.LW * cl * chn * 16
     nbytes = 4.0 * (d.N * cl * d.LH * d.LW + d.N * chn * d.HH * d.HW + cl * chn * 16)
@@ -370,16 +293,9 @@ def wgrad4x4(lo0, hi0, dw, *, lo1=None, hi1=None, act_lo=0, act_hi=0, stride=2, 
     _run(("patch_" if (d.N >= 128 and max(d.HH, d.HW) <= 34) else "") + ("head_" if cl == 1 and stride == 1 else "") + "wgrad4x4<s%d>" % stride, nbytes, flops, lib.vts_wgrad4x4,
          C.byref(d), ws.data_ptr(), L.stream())
     if defer:
-        seg = (ws, int(n // nel))
-        if prev is not None:
-            assert accumulate, "a second deferred contribution to a weight gradient must accumulate"
-            prev["segs"].append(seg)
-        else:
-            q = dict(dw=dw, nel=nel, accumulate=accumulate, segs=[seg], lane=WS_LANE)
-            _pending.append(q)
-            _pending_by_dw[dw.data_ptr()] = q
-        if wgrad_pending_bytes(WS_LANE) > FLUSH_BYTES:
-            wgrad_flush(WS_LANE)      # on this lane's stream, in stream order behind the launches that wrote the partials
+        ln.enqueue(dw, nel, accumulate, (ws, int(n // nel)))
+        if ln.pending_bytes() > FLUSH_BYTES:
+            wgrad_flush(ln.index)      # on this lane's stream, in stream order behind the launches that wrote the partials
     return dw
 
 
@@ -400,12 +316,15 @@ def tap_extract(dw4, K, a, b, dw, accumulate=False):
     return dw
 
 
+_staging = {}      # persistent staging buffers of packed / embedded weights, keyed by the weight they belong to
+
+
 def _w4_scratch(w, K, tag):
     """4x4 staging buffers for the tap blocks of `w` ([Co, Ci, K, K]); persistent (graph-capture safe)."""
     key = ("w4", w.data_ptr(), tuple(w.shape), tag)
-    buf = _ws.get(key)
+    buf = _staging.get(key)
     if buf is None:
-        buf = _ws[key] = torch.zeros(len(_tap_blocks(K)), w.shape[0], w.shape[1], 4, 4, dtype=torch.float32, device=w.device)
+        buf = _staging[key] = torch.zeros(len(_tap_blocks(K)), w.shape[0], w.shape[1], 4, 4, dtype=torch.float32, device=w.device)
     return buf
 
 
@@ -724,9 +643,9 @@ def w3x3_pack(w, mode, tag=None):
         "conv_fwd": (d1, d0, 9, 9 * d1, 0), "conv_adj": (d0, d1, 9 * d1, 9, 1), "conv_s2_adj": (d0, d1, 9 * d1, 9, 0),
         "convT_fwd": (d0, d1, 9 * d1, 9, 0), "convT_adj": (d1, d0, 9, 9 * d1, 0)}[mode]
     key = ("wt", w.data_ptr(), tuple(w.shape), mode, tag)
-    buf = _ws.get(key)
+    buf = _staging.get(key)
     if buf is None:
-        buf = _ws[key] = torch.empty(A * 9 * ((B + 3) // 4 * 4), dtype=torch.float32, device=w.device)
+        buf = _staging[key] = torch.empty(A * 9 * ((B + 3) // 4 * 4), dtype=torch.float32, device=w.device)
     _run("w3x3_pack", 8.0 * w.numel(), 0.0, L.load().vts_w3x3_pack, w.data_ptr(), A, B, sa, sb, flip, buf.data_ptr(), L.stream())
     return buf
 
@@ -737,9 +656,9 @@ def w3x3_wino_pack(w, mode, tag=None):
     A, B, sa, sb, flip = {"conv_fwd": (d1, d0, 9, 9 * d1, 0), "conv_adj": (d0, d1, 9 * d1, 9, 1)}[mode]
     lib = L.load()
     key = ("wino", w.data_ptr(), tuple(w.shape), mode, tag)
-    buf = _ws.get(key)
+    buf = _staging.get(key)
     if buf is None:
-        buf = _ws[key] = torch.empty(int(lib.vts_w3x3_wino_floats(A, B)), dtype=torch.float32, device=w.device)
+        buf = _staging[key] = torch.empty(int(lib.vts_w3x3_wino_floats(A, B)), dtype=torch.float32, device=w.device)
     _run("w3x3_wino_pack", 4.0 * (w.numel() + buf.numel()), 0.0, lib.vts_w3x3_wino_pack, w.data_ptr(), A, B, sa, sb, flip, buf.data_ptr(), L.stream())
     return buf
 
@@ -847,9 +766,9 @@ def w4x4_pack(w, mode, tag=None):
     A, B, sa, sb, flip = {"conv_fwd": (d1, d0, 16, 16 * d1, 0), "conv_adj": (d0, d1, 16 * d1, 16, 1),
                           "conv_s2_adj": (d0, d1, 16 * d1, 16, 0)}[mode]
     key = ("wt4", w.data_ptr(), tuple(w.shape), mode, tag)
-    buf = _ws.get(key)
+    buf = _staging.get(key)
     if buf is None:
-        buf = _ws[key] = torch.empty(A * 16 * ((B + 3) // 4 * 4), dtype=torch.float32, device=w.device)   # row pitch: B rounded up to 4
+        buf = _staging[key] = torch.empty(A * 16 * ((B + 3) // 4 * 4), dtype=torch.float32, device=w.device)   # row pitch: B rounded up to 4
     _run("w4x4_pack", 8.0 * w.numel(), 0.0, L.load().vts_w4x4_pack, w.data_ptr(), A, B, sa, sb, flip, buf.data_ptr(), L.stream())
     return buf
 

@@ -193,7 +193,7 @@ class ResnetGenerator(nn.Module):
             kids = {1: _ConvParams((c, c, 3, 3), c if conv_bias else 0), kb: _ConvParams((c, c, 3, 3), c if conv_bias else 0)}
             if norm == "batch":
                 kids[2], kids[kb + 1] = _BNParams(c), _BNParams(c)
-            return _Holder({"conv_block": _Holder(kids)})
+            return _Holder({"conv_block": _Holder(dict(sorted(kids.items())))})     # (state-dict order as upstream: conv, norm, conv, norm)
 
         add("pad")
         add("conv7", _ConvParams((ngf, input_nc, 7, 7), ngf if conv_bias else 0))
@@ -575,6 +575,40 @@ class MultiscaleDiscriminatorIF(MultiscaleDiscriminator):
         return res
 
 
+class NLayerDiscriminator(nn.Module):
+    """One PatchGAN as the reference's `define_D('basic' | 'n_layers')` builds it (networks.py:429-432, 1696-1750): the layers of
+    `_patchgan_layout(n_layers)` in ONE nn.Sequential `model` (state-dict keys `model.<i>.*`), BatchNorm2d, and never a Sigmoid -- define_D
+    does not pass `use_sigmoid`, so with gan_mode 'vanilla' BCEWithLogits sees the raw map (unlike the multiscale form).  To vts.engine
+    it is a one-scale pyramid: `num_D = 1` and `layer0` is `model` (msd_forward / msd_backward / msd_multi)."""
+
+    num_D = 1
+    use_sigmoid = False
+
+    def __init__(self, input_nc, ndf=64, n_layers=3, opt=None):
+        super().__init__()
+        if n_layers < 1:
+            raise ValueError("NLayerDiscriminator: n_layers must be >= 1")
+        self.input_nc, self.ndf, self.n_layers = input_nc, ndf, n_layers
+        self.CONV_IDX, self.BN_IDX, self.STRIDE = _patchgan_layout(n_layers)
+        chans = _patchgan_channels(input_nc, ndf, n_layers)
+        self.chans = chans
+        children = {}
+        for j, ci in enumerate(self.CONV_IDX):
+            children[ci] = _ConvParams((chans[j + 1], chans[j], 4, 4), chans[j + 1])
+            if ci in self.BN_IDX:
+                children[self.BN_IDX[ci]] = _BNParams(chans[j + 1])
+        self.model = _Holder(dict(sorted(children.items())))
+
+    @property
+    def layer0(self):
+        return self.model
+
+    def forward(self, x):
+        """the prediction map [N, 1, h, w] (a tensor, not a list: as upstream)"""
+        preds, _ = engine.msd_forward(self, x, None, keep=False)
+        return preds[0]
+
+
 def init_weights(net, init_type="normal", init_gain=0.02):
     """networks.py:191-231: conv weights by `init_type`, biases 0, BatchNorm weight ~ N(1, gain)."""
     for m in net.modules():
@@ -664,8 +698,12 @@ def define_D(input_nc, ndf, netD, n_layers_D=3, norm="batch", init_type="normal"
         from .stylegan2_blocks import StyleGAN2Discriminator
         size = 2 ** int(round(math.log2(min(opt.load_size, opt.crop_size))))            # stylegan_networks.py:701-702
         return init_net(StyleGAN2Discriminator(input_nc, ndf, size), init_type, init_gain, gpu_ids, initialize_weights=False)
+    if netD in ("basic", "n_layers"):    # networks.py:429-432: one PatchGAN; 'basic' is depth 3 whatever --n_layers_D says
+        if norm != "batch":
+            raise NotImplementedError("%s discriminator is built for norm=batch only" % netD)
+        return init_net(NLayerDiscriminator(input_nc, ndf, 3 if netD == "basic" else n_layers_D, opt=opt), init_type, init_gain, gpu_ids)
     if netD != "multiscale":
-        raise NotImplementedError("Discriminator model name [%s] is not recognized (built: multiscale, stylegan2)" % netD)
+        raise NotImplementedError("Discriminator model name [%s] is not recognized (built: basic, n_layers, multiscale, stylegan2)" % netD)
     if norm != "batch":
         raise NotImplementedError("multiscale discriminator is built for normD=batch only")
     cls = MultiscaleDiscriminatorIF if getattr(opt, "getIntermFeat_D", False) else MultiscaleDiscriminator   # networks.py:1661
@@ -729,6 +767,31 @@ class GANLoss:
         slot = ops.loss_slots(1, first.device)
         plist = preds if isinstance(preds[0], (list, tuple)) else [preds[-1]]
         self.accumulate(plist, target_is_real, 1.0, slot, want_grad=False)
+        return (slot.double() / ops.LOSS_SCALE).float()
+
+
+class GANLossLastSample(GANLoss):
+    """GANLoss as the reference evaluates it on the single TENSOR a `basic` / `n_layers` discriminator returns (models/pix2pix_model.py):
+    `__call__` takes `input[-1]` (networks.py:536-542), which of a tensor [N, 1, h, w] is the map of the batch's LAST SAMPLE.  The loss is
+    that one map's; the gradient with respect to the other samples' maps is zero (they still matter through the BatchNorm statistics)."""
+
+    def accumulate(self, preds, target_is_real, coeff, slot, grad_coeff=None, want_grad=True, out_grads=None, pre_sigmoid=False):
+        grads = []
+        for i, p in enumerate(preds):
+            g = None
+            if want_grad:
+                g = out_grads[i] if out_grads is not None else torch.empty_like(p)
+                if p.shape[0] > 1:
+                    g[:-1].zero_()
+            GANLoss.accumulate(self, [p[-1:]], target_is_real, coeff, slot, grad_coeff=grad_coeff, want_grad=want_grad,
+                               out_grads=[g[-1:]] if want_grad else None, pre_sigmoid=pre_sigmoid)
+            grads.append(g)
+        return grads
+
+    def __call__(self, pred, target_is_real):
+        from vts import ops
+        slot = ops.loss_slots(1, pred.device)
+        self.accumulate([pred], target_is_real, 1.0, slot, want_grad=False)
         return (slot.double() / ops.LOSS_SCALE).float()
 
 

@@ -178,6 +178,8 @@ class Pix2PixHDModel(BaseModel):
                        "(models/pix2pixHD_model.py:592-603), so these flags fail upstream as well and there is no behaviour to restate")
         if opt.netG not in ("global", "local"):
             bad.append("netG %s (built: global, local)" % opt.netG)
+        if opt.netD in ("basic", "n_layers"):      # define_D builds these for the pix2pix baseline; this step is not wired to them
+            bad.append("netD %s (built: multiscale)" % opt.netD)
         if opt.fp16 or opt.T_resolution_multiplier != 1 or not opt.use_bg_mask:
             bad.append("fp16 / T_resolution_multiplier != 1 / use_bg_mask False")
         if opt.isTrain and opt.no_gan_loss:

@@ -206,6 +206,9 @@ class SinSKITGModel(BaseModel):
                 raise NotImplementedError("T_resolution_multiplier %d: the reference's sinskitG step cannot run with a multiplier other than 1 "
                                           "(patch sizes 32 vs %d collide in compute_D2_loss, sinskitG_model.py:1477-1484)"
                                           % (opt.T_resolution_multiplier, 32 * opt.T_resolution_multiplier))
+            for flag in ("netD", "netD2"):
+                if getattr(opt, flag) in ("basic", "n_layers"):      # define_D builds these for the pix2pix baseline; this step is not wired to them
+                    raise NotImplementedError("--%s %s: this model's step is built for the multiscale and stylegan2 discriminators" % (flag, getattr(opt, flag)))
             if "D" in self.model_names:
                 self.netD = networks.define_D(opt.image_nc + (opt.sketch_nc if self.use_cGAN else 0), opt.ndf, opt.netD, opt.n_layers_D, opt.normD,
                                               opt.init_type, opt.init_gain, opt.no_antialias, num_D=opt.num_D_D1,

@@ -461,6 +461,25 @@ int vts_metric_ssim(const float* real, const float* fake, int NC, int H, int W, 
 int64_t vts_frechet_ws_floats(void);
 int vts_frechet_distance(const float* feat1, const float* feat2, int D, int64_t P1, int64_t P2, float* out, float* ws, void* stream);
 
+/* The same distance for npairs pairs in three launches (the baselines' metrics on a batch: one pair per image, two per tactile patch).
+ * Pair i reads feat1 + i * stride1 and feat2 + i * stride2 (strides in floats, >= D * P; the gaps are never read) and writes out[i].
+ * Moments: one launch over (position chunk, side, pair) and a fixed-order final pass per (side, pair), in float64.  Square root: one
+ * 256-thread workgroup per pair keeps Y, Z and T = 3I - ZY in LDS (three double[64][66] arrays, 101,376 B: needs the 160 KiB LDS of
+ * gfx950) for the whole coupled Newton-Schulz iteration, the products on v_mfma_f64_16x16x4_f64, and writes the final scalar.  The
+ * iteration runs at most 60 steps and ends once tr Y -- the returned quantity -- moves by less than 1e-9 of itself; a rank-deficient
+ * S1 S2 (constant regions in a generated patch) would diverge beyond that point, where vts_frechet_distance returns NaN.  No host
+ * work or synchronisation per pair and a workspace sized by npairs alone (vts_frechet_batched_ws_floats(npairs) floats, 8-byte
+ * aligned), so the call can be captured in a HIP graph.  out[i] does not depend on npairs or on i (bitwise), and repeats bitwise. */
+int64_t vts_frechet_batched_ws_floats(int npairs);
+int vts_frechet_distance_batched(const float* feat1, const float* feat2, int D, int64_t P1, int64_t P2, int npairs, int64_t stride1,
+                                 int64_t stride2, float* out, float* ws, void* stream);
+
+/* Crop matrix of T_FID (models/tactile_patch_fid.py:88-154 TactilePatchFID: the Fréchet distance over the 18-dimensional valid 3 x 3
+ * crops of 2-channel tactile patches).  src [N, 2, H, W] -> out [18, N (H-2) (W-2)], channel-major as vts_frechet_distance* reads it:
+ * row c * 9 + fh * 3 + fw (Im2col's order), column n (H-2)(W-2) + y (W-2) + x holds src[n][c][y + fh][x + fw], clamped to [0, 1]
+ * when clamp01 (the fake side, models/model_utils.py:517). */
+int vts_tfid_features(const float* src, int N, int H, int W, int clamp01, float* out, void* stream);
+
 /* Network input of the SIFID metrics (models/model_utils.py:481-488 I_SIFID, :541-555 T_SIFID; InceptionV3.forward's 2x - 1,
  * models/inception.py:135): out [N,3,OH,OW] from channels c0.. of src [N,*,IH,IW] (C = 3, or C = 1 tiled three times), nearest
  * resize as F.interpolate's default.  lohi != NULL (device {min, max} of the real image): v -> 2 * clamp?((v - lo) / (hi - lo)) - 1

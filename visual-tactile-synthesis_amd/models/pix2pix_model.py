@@ -19,7 +19,7 @@ import os
 import torch
 
 from vts.misc import str2bool
-from vts import engine, ops
+from vts import engine, metrics, ops
 from vts.ops import Act
 from vts.optim import FlatAdam, FlatParams
 
@@ -48,6 +48,9 @@ class Pix2PixModel(BaseModel):
     def modify_commandline_options(parser, is_train=True):
         add_model_flags(parser, MODEL_FLAGS)
         parser.add_argument("--use_hip_graph", type=B, default=True)   # not a reference flag: replay captured HIP graphs
+        # not reference flags: weight files of the optional metric networks (upstream downloads them) and --eval_T_FID (T_FID is known to
+        # compute_evaluation_metric but in none of upstream's metric lists)
+        metrics.add_metric_flags(parser)
         parser.set_defaults(norm="batch", netG="resnet_9blocks", dataset_mode="aligned", dataset="patchskit", crop_size=1536)
         verbose_freq = 320
         if is_train:
@@ -281,6 +284,11 @@ class Pix2PixModel(BaseModel):
         for i, name in enumerate(LOSS_SLOTS):
             setattr(self, "loss_" + name, vals[i])
         return BaseModel.get_current_losses(self)
+
+    def compute_metrics(self, prefix=""):
+        """the evaluation metrics of the outputs of the last forward() / test() (pix2pix_model.py:572-590 -> compute_evaluation_metric):
+        vts/metrics.py, shared by the three baselines"""
+        return metrics.model_metrics(self, prefix)
 
     def compute_visuals(self):
         pass

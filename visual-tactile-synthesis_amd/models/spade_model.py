@@ -21,7 +21,7 @@ import os
 import torch
 
 from vts.misc import str2bool
-from vts import engine, ops
+from vts import engine, metrics, ops
 from vts.optim import FlatAdam, FlatParams
 
 from . import networks
@@ -69,6 +69,9 @@ class SPADEModel(BaseModel):
             parser.add_argument("--" + name, action="store_true", default=False)
         parser.add_argument("--no_TTUR", action=_NoTTUR)
         parser.add_argument("--use_hip_graph", type=B, default=True)   # not a reference flag: replay captured HIP graphs
+        # not reference flags: weight files of the optional metric networks (upstream downloads them) and --eval_T_FID (T_FID is known to
+        # compute_evaluation_metric but in none of upstream's metric lists)
+        metrics.add_metric_flags(parser)
         # not a reference flag: torchvision vgg19 state dict for VGGLoss (the reference downloads it, models/networks.py:2040); without a
         # file the term runs on seeded stand-in weights and `loss_vgg_pretrained` says so
         parser.add_argument("--vgg_weights", type=str, default="")
@@ -224,6 +227,7 @@ class SPADEModel(BaseModel):
             masks = self._load("I_masks", torch.as_tensor(input["I_masks"]).reshape(-1, 1, h, w))
             self.real_T = ops.mask_mul(T, masks, out=T)
             self.real_gx, self.real_gy = self.real_T[:, 0:1], self.real_T[:, 1:2]
+            self.T_coords = None if self.opt.return_patch else input.get("T_coords")      # full images: where compute_metrics cuts the fake patches
 
     # ------------------------------------------------------------------ forward
     def forward(self, infer=False, keep=False):
@@ -334,6 +338,11 @@ class SPADEModel(BaseModel):
         for i, name in enumerate(LOSS_SLOTS):
             setattr(self, "loss_" + name, vals[i])
         return BaseModel.get_current_losses(self)
+
+    def compute_metrics(self, prefix=""):
+        """the evaluation metrics of the outputs of the last forward() / test() (spade_model.py:806-822 -> compute_evaluation_metric):
+        vts/metrics.py, shared by the three baselines"""
+        return metrics.model_metrics(self, prefix)
 
     def compute_visuals(self):
         pass

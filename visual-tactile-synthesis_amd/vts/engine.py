@@ -2211,6 +2211,56 @@ def sifid_tactile(net, real_T, fake_T, size=299):
     return ((vals[0] + vals[1]) * 0.5).mean()
 
 
+def sifid_pairs_batched(net, a, b, batch=16):
+    """sifid_pairs for a batch (the baselines' metrics): Inception block 0 on slices of `batch` images, then ONE batched Frechet call per
+    slice (ops.frechet_distance_batched: three launches for all its pairs); device tensor [N]"""
+    n = a.shape[0]
+    out = torch.empty(n, dtype=torch.float32, device=a.device)
+    for i0 in range(0, n, batch):
+        fa, fb = inception_block0(net, a[i0:i0 + batch]), inception_block0(net, b[i0:i0 + batch])
+        k, d = fa.shape[:2]
+        out[i0:i0 + k].copy_(ops.frechet_distance_batched(fa.reshape(k, d, -1), fb.reshape(k, d, -1)))
+    return out
+
+
+def sifid_images_batched(net, real_I, fake_I, batch=16):
+    """I_SIFID of a batch of images (model_utils.py:481-493): min-max by the range of the whole REAL batch, fake side clamped, one
+    distance per image, mean over images"""
+    lohi = ops.minmax(real_I)
+    a = ops.sifid_input(real_I, 0, 3, lohi=lohi)
+    b = ops.sifid_input(fake_I, 0, 3, lohi=lohi, clamp01=True)
+    return sifid_pairs_batched(net, a, b, batch).mean()
+
+
+def sifid_tactile_batched(net, real_T, fake_T, size=299, batch=16):
+    """T_SIFID (model_utils.py:541-555) as sifid_tactile, the per-patch distances from batched Frechet calls"""
+    vals = []
+    for c in (0, 1):
+        a = ops.sifid_input(real_T, c, 1, size=(size, size))
+        b = ops.sifid_input(fake_T, c, 1, size=(size, size), clamp01=True)
+        vals.append(sifid_pairs_batched(net, a, b, batch))
+    return ((vals[0] + vals[1]) * 0.5).mean()
+
+
+def tactile_patch_fid(real_T, fake_T, reduction="none", clamp_fake=True):
+    """T_FID (models/tactile_patch_fid.py:119-154 TactilePatchFID): Frechet distance over the 18-dimensional valid 3 x 3 crops of the
+    2-channel patches [N, 2, h, w]; clamp_fake: the fake side clamped to [0, 1] as compute_evaluation_metric does first (model_utils.py:517).
+    reduction 'none': one distance over the crops of all patches (what compute_evaluation_metric reports); 'mean': one distance per
+    patch pair, all in one batched call, then their mean.  Device scalar."""
+    n, _, h, w = real_T.shape
+    if fake_T.shape[0] != n and reduction == "mean":
+        raise ValueError("The number of images in the two groups are not equal")
+    f1, f2 = ops.tfid_features(real_T.contiguous()), ops.tfid_features(fake_T.contiguous(), clamp01=clamp_fake)
+    if reduction == "none":
+        return ops.frechet_distance_batched(f1.unsqueeze(0), f2.unsqueeze(0))[0]
+    if reduction != "mean":
+        raise NotImplementedError("reduction %s is not implemented" % reduction)
+    # [18, N P] -> [N, 18, P]: the crops of one patch are one pair's feature set (a copy: plumbing)
+    f1 = f1.view(18, n, -1).permute(1, 0, 2).contiguous()
+    f2 = f2.view(18, n, -1).permute(1, 0, 2).contiguous()
+    return ops.frechet_distance_batched(f1, f2).mean()
+
+
 # ======================================================================================================================
 # SPADE generator (`--netG spade`; reference models/networks.py:2075-2200, models/architecture.py:21-68, models/normalization.py:68-112)
 # Every 3x3 convolution reads a pre-padded operand (the modulate kernel stores that layout directly); layers of >= 64 x 64 channels

@@ -1292,6 +1292,32 @@ def frechet_distance(f1, f2):
     return out
 
 
+def frechet_distance_batched(f1, f2):
+    """Frechet distances of n pairs of channel-major feature sets [n, D, P1] / [n, D, P2] (D <= 64) in one batched call
+    (vts_frechet_distance_batched: three launches for all pairs); the batch stride is taken from the tensors; device tensor [n]"""
+    lib = L.load()
+    n, d, p1 = f1.shape
+    p2 = f2.shape[2]
+    assert f2.shape[0] == n and f2.shape[1] == d and f1.dtype == torch.float32 and f2.dtype == torch.float32
+    assert f1.stride(2) == 1 and f2.stride(2) == 1 and f1.stride(1) == p1 and f2.stride(1) == p2
+    ws = workspace(lib.vts_frechet_batched_ws_floats(n), f1.device)
+    out = torch.empty(n, dtype=torch.float32, device=f1.device)
+    L.check(lib.vts_frechet_distance_batched(f1.data_ptr(), f2.data_ptr(), d, p1, p2, n, f1.stride(0) if n > 1 else d * p1,
+                                             f2.stride(0) if n > 1 else d * p2, out.data_ptr(), ws.data_ptr(), L.stream()),
+            "vts_frechet_distance_batched")
+    return out
+
+
+def tfid_features(src, clamp01=False):
+    """crop matrix [18, N (h-2) (w-2)] of TactilePatchFID from tactile patches [N, 2, h, w] (vts_tfid_features)"""
+    lib = L.load()
+    n, c, h, w = src.shape
+    assert c == 2 and src.is_contiguous() and src.dtype == torch.float32
+    out = torch.empty(18, n * (h - 2) * (w - 2), dtype=torch.float32, device=src.device)
+    L.check(lib.vts_tfid_features(src.data_ptr(), n, h, w, int(clamp01), out.data_ptr(), L.stream()), "vts_tfid_features")
+    return out
+
+
 def minmax(x):
     """device tensor {min x, max x}"""
     lib = L.load()

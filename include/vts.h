@@ -435,6 +435,30 @@ int vts_modconv_weight_bwd(const float* w, const float* g, int Cout, int Cin, in
 int vts_adain(const float* x, const float* s, int NC, int HW, float eps, float* out, void* stream);
 int vts_adain_bwd(const float* g, const float* x, const float* s, int NC, int HW, float eps, float* dx, float* ds, void* stream);
 
+/* The tiled style code of an Up block as a 16-class bias (CustomUnetGenerator.forward with --num_layer_style_code > 1 in concat + tile
+ * mode, models/networks.py:1600-1623: the code tiled to [N, K, h, w] and concatenated in front of ConvTranspose2d(4, stride 2, pad 1)).
+ * The tile is constant over the map, so its term of the output depends only on the position class of (oy, ox): per axis
+ * {first, other even, other odd, last}, 4 x 4 classes.  With r = max(code, 0) (the block's ReLU):
+ *   vts_style_bias      out[n,co,oy,ox] = act_out(out[n,co,oy,ox] + sum_{taps of class(oy,ox)} sum_c r[n,c] w[c,co,ky,kx])  in place;
+ *                       w = the style rows of the weight, [K][Cout][4][4] contiguous; act_out NONE | TANH; OH = 2 IH, OW = 2 IW
+ *   vts_style_bias_bwd  dw[c,co,ky,kx] (+)= sum_n r[n,c] * (sum of g[n,co] over the positions whose class contains the tap),
+ *                       g = gradient w.r.t. the block's pre-norm / pre-tanh output; fixed summation order (no float atomics)
+ * out / g take a batch stride (channel slices of a wider tensor).  ws: vts_style_bias_ws_floats(N, Cout, OH) floats serve both.
+ * No tile is materialised; d/d code is not produced (tile mode reports none, as at the innermost level). */
+int64_t vts_style_bias_ws_floats(int N, int Cout, int OH);
+int vts_style_bias(const float* code, int N, int K, const float* w, int Cout, int OH, int OW, float* out, int64_t out_nstride,
+                   int act_out, float* ws, void* stream);
+int vts_style_bias_bwd(const float* g, int64_t g_nstride, const float* code, int N, int K, int Cout, int OH, int OW, float* dw,
+                       int accumulate, float* ws, void* stream);
+
+/* nn.Linear(K, P, bias=False) of style_code_mapping<j> (models/networks.py:1459-1465) at the outer decoder levels, where P = h w C
+ * reaches 81920: z[n,p] = sum_k x[n,k] w[p,k];  dw[p,k] (+)= sum_n dz[n,p] x[n,k];  dx[n,k] = sum_p dz[n,p] w[p,k] (dx may be NULL;
+ * else ws holds vts_style_linear_ws_floats floats; fixed summation order). */
+int64_t vts_style_linear_ws_floats(int N, int K, int P);
+int vts_style_linear(const float* x, const float* w, int N, int K, int P, float* z, void* stream);
+int vts_style_linear_bwd(const float* dz, const float* x, const float* w, int N, int K, int P, float* dw, int accumulate, float* dx,
+                         float* ws, void* stream);
+
 /* ---- Evaluation metrics that need no pretrained network (models/model_utils.py:431-561 compute_evaluation_metric) ----
  * vts_minmax:          out2 = {min x, max x}
  * vts_metric_psnr:     I_PSNR (:481-496): both images mapped with the REAL image's range {lo, hi} (range2, device memory) to

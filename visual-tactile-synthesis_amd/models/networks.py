@@ -105,6 +105,15 @@ class CustomUnetGenerator(nn.Module):
             self.num_layer_style_code = num_downs if nl == -1 else nl
             # channels of the style map of layer i (networks.py:1446-1457): the code itself (tile), ngf // 2 (project), ngf * 8 (adain)
             self.style_nc = ngf * 8 if self.style_mode == "adain" else (opt.style_code_dim if self.style_mapping == "tile" else ngf // 2)
+            if self.style_mode == "adain":
+                # every style map has ngf * 8 channels (networks.py:1446-1449) and AdaIN needs the content's count: the reference dies
+                # with an AssertionError (thirdparty/AdaIN/function.py:16) at the first level whose input is narrower
+                for i in range(num_downs - 1, num_downs - 1 - self.num_layer_style_code, -1):
+                    c_in = ngf * min(2 ** i, 8)
+                    if c_in != self.style_nc:
+                        raise ValueError("style_code_mode adain with num_layer_style_code %d: channel mismatch at up%d, whose content has %d "
+                                         "channels while the style map has %d (ngf * 8); at most %d levels can take it"
+                                         % (self.num_layer_style_code, i, c_in, self.style_nc, num_downs - 1 - i))
             if self.style_mapping == "project":
                 # style_code_mapping<j> = Linear(style_dim, out_size^2 * nc, bias=False) -> BatchNorm1d | InstanceNorm1d -> ReLU for
                 # up layer i = num_downs - 1 - j (networks.py:1444-1465).  In tile mode the reference creates the same Linear layers

@@ -443,9 +443,11 @@ class SinSKITGModel(BaseModel):
     def _tile_style_code(self, phase, n, h, w):
         G = self.netG
         if getattr(G, "use_style", False) and getattr(G, "style_mapping", "") == "tile":
-            # the tiled style code (networks.py:1600-1623) depends on the batch only: tiled here, once per batch, into persistent buffers
+            # the tiled style code (networks.py:1600-1623) depends on the batch only: tiled here, once per batch, into a persistent buffer.
+            # Only the innermost level reads a tile; at the other styled levels (num_layer_style_code > 1) the engine adds the code's
+            # term as a 16-class bias (ops.style_bias) and no tile exists.
             self._style_tiles = {}
-            for i in range(G.num_downs - G.num_layer_style_code, G.num_downs):
+            for i in range(max(G.num_downs - G.num_layer_style_code, G.num_downs - 1), G.num_downs):
                 hh, ww = h >> (i + 1), w >> (i + 1)
                 t = self._buf("%s_style_tile%d" % (phase, i), (n, self.style_code.shape[1], hh, ww))
                 t.copy_(self.style_code.to(torch.float32)[:, :, None, None].expand(-1, -1, hh, ww))

@@ -40,7 +40,7 @@ def _as_act(x):
 # =====================================================================================
 
 class UnetCtx:
-    __slots__ = ("x", "feats", "ups", "g_out", "style", "style_ctx", "adain_in", "dstyle")
+    __slots__ = ("x", "feats", "ups", "g_out", "style", "style_ctx", "adain_in", "adain_src", "bias_levels", "dstyle")
 
 
 def dropout_layers(G):
@@ -85,17 +85,19 @@ def unet_forward(G, x, style_code=None, keep=True, style_tiles=None, dropout_mas
     if style_code is not None:
         if not G.use_style:
             raise ValueError("generator was built without style code support")
-        style = style_code.to(torch.float32)
+        style = style_code.to(torch.float32).contiguous()
     g_out = _empty(n, 5, h, w, dev)
     ups = {}
     extras = {}
     style_ctx = {}
+    bias_levels = set()     # concat + tile below the innermost level: the tile's term of the output is a 16-class bias, no tile exists
     for i in range(nd):
         if style is not None and i >= nd - G.num_layer_style_code:
-            if i not in (0, nd - 1):
-                raise NotImplementedError("style code on a skip-connected layer needs a third concat source")
             hh, ww = h >> (i + 1), w >> (i + 1)
             if G.style_mapping == "tile":
+                if i != nd - 1:
+                    bias_levels.add(i)
+                    continue
                 t = style_tiles.get(i) if style_tiles else None
                 extras[i] = Act(t if t is not None else style[:, :, None, None].expand(-1, -1, hh, ww).contiguous())
             else:
@@ -118,8 +120,24 @@ def unet_forward(G, x, style_code=None, keep=True, style_tiles=None, dropout_mas
             out = g_out[:, c0:c0 + outer]
         else:
             out = _empty(n, outer, hh * 2, ww * 2, dev)
-        r = ops.conv4x4(inp, blk.weight, 16, outer * 16, outer, out, in1=skip if skip is not None else extra, bias=blk.bias,
-                        stride=2, pad=1, transposed=True, act_in=RELU, act_out=TANH if i == 0 else 0, instance_norm=i != 0)
+        tiled = i in bias_levels
+        if tiled or (skip is not None and extra is not None):
+            # three concat sources, ReLU(cat[x, style_i, skip_i]) (unet_parts_custom.py:61-79, networks.py:1620-1623): every source owns
+            # a contiguous block of rows of the [Cin, Cout, 4, 4] weight, so each is one accumulating launch on its row block; the
+            # tiled code's term is the class bias.  The statistics follow on the sum (a launch's fused ones would miss the other terms).
+            c_x, rows, wflat = inp.data.shape[1], outer * 16, blk.weight.view(-1)
+            kw = dict(stride=2, pad=1, transposed=True, act_in=RELU)
+            ops.conv4x4(inp, blk.weight, 16, rows, outer, out, bias=blk.bias, **kw)
+            if extra is not None:
+                ops.conv4x4(extra, wflat[c_x * rows:], 16, rows, outer, out, accumulate=True, **kw)
+            if skip is not None:
+                ops.conv4x4(skip, wflat[(c_x + G.style_nc) * rows:], 16, rows, outer, out, accumulate=True, **kw)
+            if tiled:
+                ops.style_bias(style, wflat[c_x * rows:(c_x + G.style_nc) * rows], out, act_out=TANH if i == 0 else 0)
+            r = ops.norm_stats(out, 0) if i != 0 else None
+        else:
+            r = ops.conv4x4(inp, blk.weight, 16, outer * 16, outer, out, in1=skip if skip is not None else extra, bias=blk.bias,
+                            stride=2, pad=1, transposed=True, act_in=RELU, act_out=TANH if i == 0 else 0, instance_norm=i != 0)
         res = Act(out) if i == 0 else r
         drop = None
         if i in drop_layers:
@@ -139,15 +157,25 @@ def unet_forward(G, x, style_code=None, keep=True, style_tiles=None, dropout_mas
 
     nls = G.num_layer_separate
     xm = feats[nd - 1]
-    adain_in = {}
+    adain_in, adain_src = {}, {}
+    is_adain = G.style_mode == "adain" and bool(style_ctx)
+    if is_adain and min(style_ctx) < nls - 1:
+        raise NotImplementedError("adain style conditioning of up%d inside the separate decoders (num_layer_style_code %d with num_layer_separate %d): "
+                                  "the tactile chain's own x_T = adain(x_T, style) (networks.py:1629-1630) is not built" % (min(style_ctx), G.num_layer_style_code, nls))
+
+    def adain_at(i, xm):
+        """x = adaptive_instance_normalization(x, style map) in front of up<i> (networks.py:1624-1630); a content that carries a deferred
+        InstanceNorm affine (the block above) is materialised"""
+        x_raw = ops.pad_affine(xm, (0, 0, 0, 0), 0) if (xm.scale is not None) else xm.data
+        adain_in[i], adain_src[i] = x_raw, xm
+        return Act(ops.adain(x_raw, style_ctx[i][-1]))
+
     for i in range(nd - 1, nls - 1, -1):      # shared trunk
-        if i in style_ctx and G.style_mode == "adain":     # x = adaptive_instance_normalization(x, style map) (networks.py:1624-1630)
-            if i != nd - 1:
-                raise NotImplementedError("adain style conditioning is built for the innermost layer (num_layer_style_code 1)")
-            x_raw = ops.pad_affine(xm, (0, 0, 0, 0), 0) if (xm.scale is not None) else xm.data
-            adain_in[i] = x_raw
-            xm = Act(ops.adain(x_raw, style_ctx[i][-1]))
+        if is_adain and i in style_ctx:
+            xm = adain_at(i, xm)
         xm = up(i, "up%d" % i, xm)
+    if is_adain and nls > 0 and (nls - 1) in style_ctx and (nls - 1) not in adain_in:
+        xm = adain_at(nls - 1, xm)            # the split point: up<i> and up<i>_T both read the one adain(x) (x_T is x there)
 
     def chain(lane):                          # the visual (lane 0) and tactile (lane 1) decoders are independent chains
         x = xm
@@ -160,7 +188,7 @@ def unet_forward(G, x, style_code=None, keep=True, style_tiles=None, dropout_mas
         return g_out, None
     ctx = UnetCtx()
     ctx.x, ctx.feats, ctx.ups, ctx.g_out, ctx.style = (x, x_extra), feats, ups, g_out, style
-    ctx.style_ctx, ctx.adain_in, ctx.dstyle = style_ctx, adain_in, None
+    ctx.style_ctx, ctx.adain_in, ctx.adain_src, ctx.bias_levels, ctx.dstyle = style_ctx, adain_in, adain_src, bias_levels, None
     return g_out, ctx
 
 
@@ -290,6 +318,12 @@ def unet_backward_c(G, ctx, d_raw, side_stream=None):
     L.check(lib.vts_unet_backward(C.byref(d), C.byref(g), ws.data_ptr(), ws.numel(), L.stream()), "vts_unet_backward")
 
 
+def _style_linear_wide(P, k):
+    """the Linear of a style mapping as a 1 x 1 convolution embeds its weight in 4 x 4 tap blocks (16 x the size, twice: forward and
+    gradient): fine for the innermost maps, not for the outer levels of num_layer_style_code > 1 (81920 x 512 at a 128 x 128 map)"""
+    return P * k > (1 << 21)
+
+
 def _style_map_forward(G, j, style, hh, ww):
     """style_code_mapping<j> (networks.py:1459-1465, 1611-1615): Linear(style_dim, P, bias=False) -> BatchNorm1d (batch_size > 1) |
     InstanceNorm1d -> ReLU, reshaped to [N, P / (h w), h, w].  The Linear is a 1 x 1 convolution on a 1 x 1 map; BatchNorm1d over
@@ -305,7 +339,10 @@ def _style_map_forward(G, j, style, hh, ww):
                          "input (networks.py:1432, 1458)" % (j, P, hh, ww, 1536))
     z = _empty(n, P, 1, 1, style.device)
     sv = style.reshape(n, k, 1, 1).contiguous()
-    ops.convk(sv, lin.weight.view(P, k, 1, 1), z, pad=0)
+    if _style_linear_wide(P, k):
+        ops.style_linear(sv.view(n, k), lin.weight, out=z.view(n, P))
+    else:
+        ops.convk(sv, lin.weight.view(P, k, 1, 1), z, pad=0)
     if bn is not None:
         if G.training:
             a = ops.norm_stats(z, 1, gamma=bn.weight, beta=bn.bias, running_mean=bn.running_mean, running_var=bn.running_var, nbt=bn.num_batches_tracked)
@@ -337,12 +374,23 @@ def _style_map_backward(G, sctx, d_map, want_dstyle=False):
     else:
         ops.norm_bwd(dz, a, 0)
     dz = dz.view(n, P, 1, 1)
+    if _style_linear_wide(P, k):
+        return ops.style_linear_bwd(dz.view(n, P), sv.view(n, k), lin.weight, lin.weight.grad, want_dx=want_dstyle)
     ops.wgradk(dz, sv, lin.weight.grad.view(P, k, 1, 1), pad=0)
     if not want_dstyle:
         return None
     ds = torch.empty_like(sv)
     ops.convk_bwd_data(dz, lin.weight.view(P, k, 1, 1), ds, pad=0)
     return ds.view(n, k)
+
+
+def _add_dstyle(ctx, ds):
+    """ctx.dstyle += one style mapping's d/d style_code [N, style_dim]"""
+    if ctx.dstyle is None:
+        ctx.dstyle = ds
+    else:
+        n = ds.shape[0]
+        ctx.dstyle = ops.pad_affine(ctx.dstyle.view(n, -1, 1, 1), (0, 0, 0, 0), 0, res=ds.view(n, -1, 1, 1)).view(n, -1)
 
 
 def unet_backward(G, ctx, d_raw):
@@ -395,9 +443,12 @@ def _unet_backward(G, ctx, d_raw, part="all", state=None):
         """the block's primary input is a Dropout output: its gradient is not yet the gradient of a normalised map (no fused sums)"""
         return id(inp) in dropped
 
-    def up_bwd(i, name, dx, dfeat, wq, lane_mode=False):
+    dmaps = {}               # styled level -> grad wrt its projected style map (both decoders' parts summed): feeds style_code_mapping<j>
+
+    def up_bwd(i, name, dx, dfeat, wq, dmaps, lane_mode=False):
         """backward of one up block: weight gradient (through wq: side queue, or inline inside a lane), gradient w.r.t.
-        the block input into dx / dfeat[nd-1], gradient w.r.t. the skip feature into dfeat[i]"""
+        the block input into dx / dfeat[nd-1], gradient w.r.t. the skip feature into dfeat[i], gradient w.r.t. a concatenated
+        projected style map into dmaps[i]"""
         skip = None if i in (0, nd - 1) else feats[i]
         blk = getattr(G, name).conv
         inp, outp, extra, drop = ctx.ups[name]
@@ -416,13 +467,26 @@ def _unet_backward(G, ctx, d_raw, part="all", state=None):
                 ops.norm_bwd(g, outp, 0)
         gop = Act(g)
         second = skip if skip is not None else extra
-        wq(lambda: ops.wgrad4x4(inp, gop, blk.weight.grad, lo1=second, act_lo=RELU, stride=2, pad=1), g)
+        c_in0 = inp.data.shape[1]
+        tiled = i in ctx.bias_levels
+        three = tiled or (skip is not None and extra is not None)      # ReLU(cat[x, style_i, skip_i]): one row block of the weight per source
+        c_sk = c_in0 + (G.style_nc if three else 0)                    # first weight row of the skip source
+        if three:
+            rows, dwf = outer * 16, blk.weight.grad.view(-1)
+            wq(lambda: ops.wgrad4x4(inp, gop, dwf[:c_in0 * rows], act_lo=RELU, stride=2, pad=1), g)
+            if extra is not None:
+                wq(lambda: ops.wgrad4x4(extra, gop, dwf[c_in0 * rows:c_sk * rows], act_lo=RELU, stride=2, pad=1), g)
+            if tiled:      # the tiled code's rows: class sums of g (no tile is read)
+                wq(lambda: ops.style_bias_bwd(g, ctx.style, dwf[c_in0 * rows:c_sk * rows]), g)
+            if skip is not None:
+                wq(lambda: ops.wgrad4x4(skip, gop, dwf[c_sk * rows:], act_lo=RELU, stride=2, pad=1), g)
+        else:
+            wq(lambda: ops.wgrad4x4(inp, gop, blk.weight.grad, lo1=second, act_lo=RELU, stride=2, pad=1), g)
         if i == 0:
             wq(lambda: ops.channel_sum(g, blk.bias.grad), g)
         # else: the bias feeds an InstanceNorm, so its gradient is identically zero (the norm removes any
         # per-channel constant).  The reference computes ~1e-9 rounding noise there; the flat gradient
         # buffer is zero-initialised and this slot is never written, i.e. exactly 0.
-        c_in0 = inp.data.shape[1]
         # grad wrt the primary input (normalised output of the previous up block, or feats[nd-1])
         if i == nd - 1:
             tgt, acc = add_grad_list(dfeat, nd - 1, inp.data.shape, dev)
@@ -430,26 +494,37 @@ def _unet_backward(G, ctx, d_raw, part="all", state=None):
             tgt, acc = add_grad(dx, id(inp), inp.data.shape)
         # (the tensor goes straight into the InstanceNorm backward of the block below unless it is the un-normalised innermost feature
         #  or the split point i == nls - 1, where up{i} and up{i}_T BOTH contribute -- as two lanes or, with VTS_PARALLEL_SCALES=0, as
-        #  two accumulating calls: the fused sums (and the k-split epilogue's fused backward) would see only one part of the gradient)
+        #  two accumulating calls: the fused sums (and the k-split epilogue's fused backward) would see only one part of the gradient;
+        #  nor where the input is an AdaIN output: its gradient passes through adain_bwd before it reaches that InstanceNorm backward)
         ops.conv4x4(gop, blk.weight, outer * 16, 16, c_in0, tgt, stride=2, pad=1, dmask=inp, dmask_act=RELU, accumulate=acc,
-                    bwd_sums="in" if (i != nd - 1) and not (nls > 0 and i == nls - 1) and not dropped_input(inp) else False)
+                    bwd_sums="in" if (i != nd - 1) and not (nls > 0 and i == nls - 1) and not dropped_input(inp) and i not in ctx.adain_in else False)
         if skip is not None:
             tgt, acc = add_grad_list(dfeat, i, skip.data.shape, dev)
-            wv = blk.weight.view(-1)[c_in0 * outer * 16:]
+            wv = blk.weight.view(-1)[c_sk * outer * 16:]
             ops.conv4x4(gop, wv, outer * 16, 16, skip.data.shape[1], tgt, stride=2, pad=1, dmask=skip, dmask_act=RELU,
                         accumulate=acc)
-        elif extra is not None and i in ctx.style_ctx and G.style_mode == "concat":
-            # projected style map as the second concat source: its gradient feeds style_code_mapping<j>'s parameters
-            d_map = torch.empty_like(extra.data)
+        if extra is not None and i in ctx.style_ctx and G.style_mode == "concat":
+            # projected style map as a concat source: its gradient (backward-data on its row block) feeds style_code_mapping<j>'s
+            # parameters, after the parts of up<i> and up<i>_T have been summed
+            d_map, acc = add_grad(dmaps, i, extra.data.shape)
             wv = blk.weight.view(-1)[c_in0 * outer * 16:]
-            ops.conv4x4(gop, wv, outer * 16, 16, extra.data.shape[1], d_map, stride=2, pad=1, dmask=extra, dmask_act=RELU)
-            ctx.dstyle = _style_map_backward(G, ctx.style_ctx[i], d_map, want_dstyle=True)
+            ops.conv4x4(gop, wv, outer * 16, 16, extra.data.shape[1], d_map, stride=2, pad=1, dmask=extra, dmask_act=RELU, accumulate=acc)
+
+    def adain_bwd_at(i):
+        """up<i> (and up<i>_T at the split point) consumed adain(x, style map), x the normalised output of up<i+1>: the gradient of
+        that input splits into the content part, which goes on into the InstanceNorm backward of up<i+1>, and the style part"""
+        if i not in ctx.adain_in or i == nd - 1:      # (the innermost level's content is feats[nd-1]: _unet_backward_encoder)
+            return
+        gin = dx.pop(id(ctx.ups["up%d" % i][0]))
+        dxr, dsm = ops.adain_bwd(gin.contiguous(), ctx.adain_in[i], ctx.style_ctx[i][-1])
+        dx[id(ctx.adain_src[i])] = dxr
+        dmaps[i] = dsm
 
     nls = G.num_layer_separate
     if nls > 0 and PARALLEL_SCALES:
         # the visual and the tactile decoder are independent chains: two lanes with their own gradient buffers,
         # summed where the chains share a tensor (skip features, the split point)
-        lane_dx, lane_df = [{}, {}], [[None] * nd, [None] * nd]
+        lane_dx, lane_df, lane_dm = [{}, {}], [[None] * nd, [None] * nd], [{}, {}]
 
         def inline(fn, *keep):
             fn()
@@ -461,7 +536,7 @@ def _unet_backward(G, ctx, d_raw, part="all", state=None):
             # behind the lanes instead of inside them: 5.31 - 5.34 against 5.25 - 5.28 ms (profiles/r06a_experiments.md section 2b).  The backward
             # is throughput-bound: work moved beside its chain slows the chain by as much.)
             for i in range(nls):
-                up_bwd(i, "up%d%s" % (i, "_T" if lane else ""), lane_dx[lane], lane_df[lane], inline, lane_mode=True)
+                up_bwd(i, "up%d%s" % (i, "_T" if lane else ""), lane_dx[lane], lane_df[lane], inline, lane_dm[lane], lane_mode=True)
 
         _run_lanes(2, chain)
 
@@ -472,13 +547,20 @@ def _unet_backward(G, ctx, d_raw, part="all", state=None):
             dfeat[i] = total(lane_df[0][i], lane_df[1][i])
         for key in set(lane_dx[0]) | set(lane_dx[1]):
             dx[key] = total(lane_dx[0].get(key), lane_dx[1].get(key))
+        for i in sorted(set(lane_dm[0]) | set(lane_dm[1])):
+            dmaps[i] = total(lane_dm[0].get(i), lane_dm[1].get(i))
         first_shared = nls
+        adain_bwd_at(nls - 1)
     else:
         first_shared = 0
     for i in range(first_shared, nd):
         names = ["up%d" % i] + (["up%d_T" % i] if nls >= i + 1 else [])
         for name in names:
-            up_bwd(i, name, dx, dfeat, sq.run)
+            up_bwd(i, name, dx, dfeat, sq.run, dmaps)
+        adain_bwd_at(i)
+    for i in sorted(dmaps, reverse=True):     # d/d style_code: the sum over the levels from the inside out, a fixed order (an innermost
+                                              # AdaIN level joins last, in _unet_backward_encoder)
+        _add_dstyle(ctx, _style_map_backward(G, ctx.style_ctx[i], dmaps[i], want_dstyle=True))
 
     if part == "decoder":
         sq.join()
@@ -492,7 +574,7 @@ def _unet_backward_encoder(G, ctx, dfeat, feats, nd, dev, sq):
         smap = ctx.style_ctx[nd - 1][-1]
         dxr, dsm = ops.adain_bwd(dfeat[nd - 1].contiguous(), x_raw, smap)
         dfeat[nd - 1] = dxr
-        ctx.dstyle = _style_map_backward(G, ctx.style_ctx[nd - 1], dsm, want_dstyle=True)
+        _add_dstyle(ctx, _style_map_backward(G, ctx.style_ctx[nd - 1], dsm, want_dstyle=True))
     for i in range(nd - 1, -1, -1):
         blk = getattr(G, "down%d" % i).conv
         g = dfeat[i]

@@ -156,7 +156,7 @@ SYMBOLS = [
     "vts_avgpool3s2", "vts_avgpool3s2_bwd", "vts_ganloss", "vts_l1", "vts_patch_gather", "vts_patch_scatter_bwd",
     "vts_g_post", "vts_diffaug_bs_mask", "vts_diffaug_op", "vts_diffaug_op_ws_floats", "vts_g_out_grad", "vts_g_out_grad_pool", "vts_pool_query", "vts_mask_mul", "vts_input_images_u8", "vts_spe_grid", "vts_mask_candidates",
     "vts_pad_affine", "vts_pad_bwd", "vts_blur_down", "vts_blur_down_bwd", "vts_blur_up", "vts_blur_up_bwd", "vts_tap_embed", "vts_tap_extract", "vts_tap_embed_at", "vts_tap_extract_at", "vts_w3x3_pack", "vts_conv3x3_wide", "vts_w3x3_wino_floats", "vts_w3x3_wino_pack", "vts_conv3x3_wino_ok", "vts_conv3x3_wino", "vts_conv3x3_wide_relu_pad", "vts_conv3x3_wide_mask_pad", "vts_zero_border", "vts_conv3x3_wide_ws_floats", "vts_conv3x3s2_wide", "vts_tconv3x3s2_wide", "vts_wgrad3x3_wide", "vts_wgrad3x3_wide_ws_floats", "vts_upfirdn2d_out_size", "vts_upfirdn2d", "vts_upfirdn2d_bwd", "vts_bias_act", "vts_bias_act_bwd", "vts_modconv_demod", "vts_w4x4_pack", "vts_conv4x4_flat_ok", "vts_conv4x4_wide_ws_floats", "vts_conv4x4_wide", "vts_wgrad4x4_wide_ws_floats", "vts_wgrad4x4_wide",
-    "vts_metric_ws_floats", "vts_minmax", "vts_metric_psnr", "vts_metric_tactile", "vts_metric_ssim", "vts_frechet_ws_floats", "vts_frechet_distance", "vts_frechet_batched_ws_floats", "vts_frechet_distance_batched", "vts_tfid_features", "vts_sifid_input", "vts_modconv_weight", "vts_modconv_weight_bwd", "vts_modconv_scale_dot_ws_floats", "vts_modconv_scale_dot", "vts_modconv_demod_bwd", "vts_modconv_transpose", "vts_adain", "vts_adain_bwd", "vts_resample_table",
+    "vts_metric_ws_floats", "vts_minmax", "vts_metric_psnr", "vts_metric_tactile", "vts_metric_ssim", "vts_frechet_ws_floats", "vts_frechet_distance", "vts_frechet_batched_ws_floats", "vts_frechet_distance_batched", "vts_tfid_features", "vts_sifid_input", "vts_modconv_weight", "vts_modconv_weight_bwd", "vts_modconv_scale_dot_ws_floats", "vts_modconv_scale_dot", "vts_modconv_demod_bwd", "vts_modconv_transpose", "vts_adain", "vts_adain_bwd", "vts_style_bias_ws_floats", "vts_style_bias", "vts_style_bias_bwd", "vts_style_linear_ws_floats", "vts_style_linear", "vts_style_linear_bwd", "vts_resample_table",
     "vts_mask_select", "vts_mask_sample_ranks", "vts_adam_flat", "vts_adam_flat_dev", "vts_patchnce", "vts_l2norm_rows", "vts_patch_sample", "vts_linear_rows", "vts_copy_words",
     "vts_maxpool2_relu_pad", "vts_maxpool3s2_relu_pad", "vts_s2d4_pad", "vts_maxpool2_relu_bwd", "vts_relu_mask_pad", "vts_lpips_layer", "vts_l1_relu", "vts_lpips_input", "vts_lpips_input_bwd", "vts_vgg_stack_input", "vts_vgg_stack_input_bwd",
     "vts_patch_jobs", "vts_g_post_stack", "vts_step_begin", "vts_conv4x4_bsums", "vts_norm_bwd_from_partials",
@@ -228,6 +228,10 @@ def load():
     lib.vts_spectral_norm_ws_floats.argtypes = [C.c_int, C.c_int]
     lib.vts_spectral_norm_ws_floats.restype = C.c_int64
     lib.vts_gemm_f16_ws_floats.argtypes = [C.c_int] * 3
+    lib.vts_style_bias_ws_floats.argtypes = [C.c_int] * 3
+    lib.vts_style_bias_ws_floats.restype = C.c_int64
+    lib.vts_style_linear_ws_floats.argtypes = [C.c_int] * 3
+    lib.vts_style_linear_ws_floats.restype = C.c_int64
     lib.vts_gemm_f16_ws_floats.restype = C.c_int64
     lib.vts_clip_visual_weight_halfs.argtypes = [C.POINTER(ClipVisualCfg)]
     lib.vts_clip_visual_weight_halfs.restype = C.c_int64
@@ -291,6 +295,10 @@ def load():
         "vts_adain": [vp, vp, i, i, f, vp, vp],
         "vts_resample_table": [vp, i64, i, i, vp, vp, vp, i, vp, vp, vp, i, vp, i, i, i, vp],
         "vts_adain_bwd": [vp, vp, vp, i, i, f, vp, vp, vp],
+        "vts_style_bias": [vp, i, i, vp, i, i, i, vp, i64, i, vp, vp],
+        "vts_style_bias_bwd": [vp, i64, vp, i, i, i, i, i, vp, i, vp, vp],
+        "vts_style_linear": [vp, vp, i, i, i, vp, vp],
+        "vts_style_linear_bwd": [vp, vp, vp, i, i, i, vp, i, vp, vp, vp],
         "vts_modconv_weight": [vp, i, i, i, f, f, i, vp, vp],
         "vts_modconv_weight_bwd": [vp, vp, i, i, i, f, f, i, vp, i, vp],
         "vts_metric_tactile": [vp, vp, i64, i, vp, vp, vp, vp],

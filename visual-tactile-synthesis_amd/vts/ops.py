@@ -569,6 +569,64 @@ def adain_bwd(g, x, s, eps=1e-5):
     return dx, ds
 
 
+def _plane_view_ok(t):
+    """an NCHW tensor or a channel slice of one: dense planes, any batch stride"""
+    n, c, h, w = t.shape
+    return t.dtype == torch.float32 and t.stride(3) == 1 and t.stride(2) == w and t.stride(1) == h * w
+
+
+def style_bias(code, w_rows, out, act_out=0):
+    """out <- act_out(out + the tiled style code's term of ConvTranspose2d(4, 2, 1)) in place, as a 16-class bias (vts_style_bias).
+    code [N, K]; w_rows: the K style rows of the block's weight, a contiguous view [K * Cout * 16] or [K, Cout, 4, 4]; out [N, Cout,
+    OH, OW] raw output of the other sources' launches, possibly a channel slice (batch stride)."""
+    n, k = code.shape
+    _, cout, oh, ow = out.shape
+    assert code.is_contiguous() and code.dtype == torch.float32 and w_rows.is_contiguous() and w_rows.numel() >= k * cout * 16 and _plane_view_ok(out)
+    lib = L.load()
+    ws = workspace(lib.vts_style_bias_ws_floats(n, cout, oh), out.device)
+    BSUMS.pop(out.data_ptr(), None)
+    _run("style_bias", 8.0 * n * cout * oh * ow + 4.0 * k * cout * 16, 2.0 * n * k * cout * 16, lib.vts_style_bias, code.data_ptr(), n, k, w_rows.data_ptr(), cout, oh, ow,
+         out.data_ptr(), out.stride(0), act_out, ws.data_ptr(), L.stream())
+    return out
+
+
+def style_bias_bwd(g, code, dw_rows, accumulate=False):
+    """dw_rows (+)= the weight gradient of the K style rows from g [N, Cout, OH, OW] (gradient w.r.t. the block's pre-norm / pre-tanh
+    output, possibly a channel slice): vts_style_bias_bwd, fixed summation order"""
+    n, k = code.shape
+    _, cout, oh, ow = g.shape
+    assert code.is_contiguous() and code.dtype == torch.float32 and dw_rows.is_contiguous() and dw_rows.numel() >= k * cout * 16 and _plane_view_ok(g)
+    lib = L.load()
+    ws = workspace(lib.vts_style_bias_ws_floats(n, cout, oh), g.device)
+    _run("style_bias_bwd", 4.0 * n * cout * oh * ow + 4.0 * k * cout * 16, 2.0 * n * k * cout * 16, lib.vts_style_bias_bwd, g.data_ptr(), g.stride(0), code.data_ptr(), n, k,
+         cout, oh, ow, dw_rows.data_ptr(), int(accumulate), ws.data_ptr(), L.stream())
+    return dw_rows
+
+
+def style_linear(x, w, out=None):
+    """z [N, P] = x [N, K] w [P, K]^T: the bias-free nn.Linear of style_code_mapping<j> at the outer levels (vts_style_linear)"""
+    n, k = x.shape
+    p = w.shape[0]
+    assert x.is_contiguous() and w.is_contiguous() and w.shape[1] == k and x.dtype == w.dtype == torch.float32
+    if out is None:
+        out = torch.empty(n, p, dtype=torch.float32, device=x.device)
+    _run("style_linear", 4.0 * (p * k + n * (p + k)), 2.0 * n * p * k, L.load().vts_style_linear, x.data_ptr(), w.data_ptr(), n, k, p, out.data_ptr(), L.stream())
+    return out
+
+
+def style_linear_bwd(dz, x, w, dw, want_dx=False, accumulate=False):
+    """dw [P, K] (+)= dz^T x; returns dx [N, K] = dz w when asked (vts_style_linear_bwd, fixed summation order)"""
+    n, k = x.shape
+    p = w.shape[0]
+    assert dz.shape == (n, p) and dz.is_contiguous() and x.is_contiguous() and w.is_contiguous() and dw.is_contiguous() and dw.shape == w.shape
+    lib = L.load()
+    dx = torch.empty_like(x) if want_dx else None
+    ws = workspace(lib.vts_style_linear_ws_floats(n, k, p), x.device) if want_dx else None
+    _run("style_linear_bwd", 4.0 * (2 + bool(want_dx)) * p * k, (2.0 + 2.0 * bool(want_dx)) * n * p * k, lib.vts_style_linear_bwd, dz.data_ptr(), x.data_ptr(), w.data_ptr(),
+         n, k, p, dw.data_ptr(), int(accumulate), L.ptr(dx), L.ptr(ws), L.stream())
+    return dx
+
+
 def modconv_weight(w, transpose=False, eps=1e-8):
     """style-free demodulated weight of ModulatedConv2d (stylegan_networks.py:307-317 with style None): w [1,Co,Ci,K,K] -> [Co,Ci,K,K],
     or [Ci,Co,K,K] with transpose (include/vts.h)"""

@@ -255,7 +255,8 @@ int vts_act_bwd(const float* g, const vts_operand* x, int N, int HW, int act, fl
  * `x + norm(conv_block(x))` of ResnetBlock.forward (networks.py:1322) or a plain activation. */
 int vts_pad_affine(const vts_operand* in, int N, int H, int W, int pt, int pb, int pl, int pr, int mode, int act,
                    const float* res, float* out, int64_t out_nstride, void* stream);
-/* Adjoint of the padding index map: din[n,c,i,j] (+)= sum of dpad over the padded positions that read (i,j). */
+/* Adjoint of the padding index map: din[n,c,i,j] (+)= sum of dpad over the padded positions that read (i,j).  As in the forward, a
+ * reflect pad must be smaller than the image (VTS_ERR_ARG otherwise). */
 int vts_pad_bwd(const float* dpad, int N, int C, int H, int W, int pt, int pb, int pl, int pr, int mode, float* din,
                 int accumulate, void* stream);
 
@@ -895,7 +896,8 @@ int vts_comm_destroy(void* comm);
  * vts_nearest_resize: F.interpolate(mode="nearest") (networks.py:2149, normalization.py:104): out[.,oy,ox] = x[., sy(oy), sx(ox)],
  *   s(d) = min(floor(d * in / out), in - 1) evaluated as ATen does (float scale; identity and exact halving as integer shortcuts).
  *   _bwd: din (+)= the adjoint (each source pixel gathers the destinations that read it).
- * vts_nearest_up2 / _bwd: nn.Upsample(scale_factor=2) (networks.py:2117) and its adjoint, the sum over each 2 x 2 cell.
+ * vts_nearest_up2 / _bwd: nn.Upsample(scale_factor=2) (networks.py:2117) and its adjoint, the sum over each 2 x 2 cell.  The 2H x 2W
+ *   tensor (`out` / `dout`) is accessed as float2 and must be 8-byte aligned (VTS_ERR_ARG otherwise).
  * vts_spectral_norm: torch.nn.utils.spectral_norm (architecture.py:35-39) of W = w viewed [Co][K], K = Ci * kh * kw:
  *   training != 0:  v <- W^T u / max(|W^T u|, eps);  u <- W v / max(|W v|, eps)   (one power iteration, stored in place)
  *   always:         sigma[0] = u^T W v;  w_out = w / sigma.        ws: vts_spectral_norm_ws_floats(Co, K) floats.

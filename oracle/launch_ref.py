@@ -1,5 +1,7 @@
-"""Float64 judge of the C ABI's conv / weight-gradient / normalisation semantics and of the step's glue kernels (loss, optimiser,
-pyramid, patches, post-processing, augmentation, staging, sampler), written from the formulas in include/vts.h (not from the kernels).  Checker only: the product never imports it.
+"""Float64 judge of the C ABI's conv / weight-gradient / normalisation semantics, of the step's glue kernels (loss, optimiser,
+pyramid, patches, post-processing, augmentation, staging, sampler) and of the padding / resampling / FIR operators (pad, blur, weight taps,
+table resampling, upfirdn2d, bias_act, nearest, tanh_bwd; their units are derived rounding counts, see that section), written from the
+formulas in include/vts.h (not from the kernels).  Checker only: the product never imports it.
 
 Every function returns {name: (ref, unit)} with float64 tensors: `ref` the exact value, `unit` the elementwise error scale of an
 fp32 evaluation, u * sqrt(K) * absref, where u = 2^-24, K is the number of products summed into the element and absref is the same
@@ -857,3 +859,357 @@ def worst(got, ref, unit):
     r = torch.where(torch.isfinite(got), r, torch.full_like(r, math.inf))
     i = int(torch.argmax(r))
     return float(r[i]), i
+
+
+# ---- padding, resampling and FIR operators (csrc/vts_resample.hip, the upfirdn2d / bias_act entries of csrc/vts_stylegan2.hip, the nearest /
+# tanh_bwd entries of csrc/vts_spade.hip) -------------------------------------------------------------------------------------------------
+# Units here are derived worst-case rounding counts with nothing measured in them: unit = (r + K) u absref, K = the products summed into
+# the element, r = the other roundings of the formula (an affine fmaf one, an activation slope one, a gain one, a residual or accumulate
+# add one each), absref = the same expression with every term in absolute value.  Every term of a K-term fp32 sum passes through at most
+# K roundings (its product and K - 1 adds), so a correct one-pass kernel stays within 1 unit to first order in u, in any summation
+# order; the tests allow 1.01 for the second-order terms.  The one exception is tanh, whose error depends on the device's tanhf: see TANH_E.
+SLOPE32 = {0: None, 1: float(torch.tensor(0.2, dtype=torch.float32)), 2: 0.0}      # the slope as the fp32 constant the formula carries
+
+# worst |torch.tanh(x) - tanh(x)| / (u |tanh(x)|) of PyTorch's own device kernel on the MI355X over 8.4e6 fp32 arguments in [-12, 12]
+# (2.4593, at x = -0.64956; 1.26 for |x| >= 1, 1.02 below 0.1).  The bound allows twice that plus one ulp (<= 2 u |ref|): the library's
+# tanhf and PyTorch's kernel may take different paths.
+TANH_E_MEASURED = 2.4593
+TANH_E = 2 * TANH_E_MEASURED + 2
+
+
+def affine_act(x, scale, shift, act):
+    """(value, absvalue, roundings) elementwise of act(fmaf(x, scale, shift)), x [N, C, H, W], scale / shift [N, C] or both None.
+    Roundings: the fmaf 1 (0 without an affine), the LeakyReLU slope 1 where the value is negative (ReLU and the positive side are exact).
+    act 3 (tanh): value tanh(t) and roundings = None; the caller adds tanh_unit()."""
+    x = _f64(x)
+    n, c = x.shape[:2]
+    a, r = x.abs(), torch.zeros_like(x)
+    if scale is not None:
+        s, b = _f64(scale).view(n, c, 1, 1), _f64(shift).view(n, c, 1, 1)
+        x, a, r = x * s + b, a * s.abs() + b.abs(), r + 1
+    if act == 3:
+        return torch.tanh(x), a, None
+    slope = SLOPE32[act]
+    if slope is not None:
+        neg = ~(x > 0)
+        f = torch.where(neg, torch.full_like(x, slope), torch.ones_like(x))
+        x, a = x * f, a * f
+        if slope != 0.0:
+            r = r + neg.to(r.dtype)
+    return x, a, r
+
+
+def tanh_unit(t_abs, affine, ref):
+    """error scale of tanhf(fmaf(x, a, b)): the propagated rounding of the argument, u |t| (1 - ref^2) (absent without an affine), plus
+    TANH_E u |ref| for the function itself"""
+    return (U * t_abs * (1 - ref * ref) if affine else 0.0) + TANH_E * U * ref.abs()
+
+
+def pad_index(size, lo, hi, mode):
+    """source index of every position of an axis padded by (lo, hi): mode 0 zero (-1), 1 reflect (no edge repeat), 2 replicate"""
+    t = torch.arange(-lo, size + hi)
+    if mode == 1:
+        assert lo < size and hi < size
+        s = torch.where(t < 0, -t, torch.where(t >= size, 2 * size - 2 - t, t))
+    elif mode == 2:
+        s = t.clamp(0, size - 1)
+    else:
+        s = torch.where((t < 0) | (t >= size), torch.full_like(t, -1), t)
+    return s
+
+
+def _gather2(x, sy, sx):
+    """x[..., sy, sx] with zeros where an index is -1"""
+    v = x[..., sy.clamp_min(0), :][..., sx.clamp_min(0)]
+    keep = ((sy >= 0)[:, None] & (sx >= 0)[None, :]).to(x.dtype)
+    return v * keep
+
+
+def _scatter2(g, sy, sx, h, w):
+    """adjoint of _gather2: out[..., sy[i], sx[j]] += g[..., i, j]"""
+    g = g * ((sy >= 0)[:, None] & (sx >= 0)[None, :]).to(g.dtype)
+    rows = g.new_zeros(g.shape[:-2] + (h, g.shape[-1])).index_add_(-2, sy.clamp_min(0), g)
+    return g.new_zeros(g.shape[:-2] + (h, w)).index_add_(-1, sx.clamp_min(0), rows)
+
+
+def pad_affine(x, scale, shift, pads, mode, act, res=None):
+    """vts_pad_affine: out = pad(act(x * scale + shift)) (+ res); pads (top, bottom, left, right); the zero mode pads with 0 (not act(shift)).
+    No sum: K = 0; r = affine + slope (+ 1 for the residual add)."""
+    pt, pb, pl, pr = pads
+    h, w = x.shape[-2:]
+    v, a, r = affine_act(x, scale, shift, act)
+    sy, sx = pad_index(h, pt, pb, mode), pad_index(w, pl, pr, mode)
+    ref, aa = _gather2(v, sy, sx), _gather2(a, sy, sx)
+    if act == 3:
+        unit, aa = _gather2(tanh_unit(a, scale is not None, v), sy, sx), ref.abs()
+    else:
+        unit = U * _gather2(r, sy, sx) * aa
+    if res is not None:                                  # one more rounding, of the sum
+        o = _f64(res)
+        unit = unit + U * (aa + o.abs()) if act == 3 else U * (_gather2(r, sy, sx) + 1) * (aa + o.abs())
+        ref = ref + o
+    return {"out": (ref, unit)}
+
+
+def _sum_unit(cnt, a, o):
+    """unit of a sum of cnt plain addends (cnt - 1 roundings) with absolute sum a, accumulated onto o (one more) or not (o None)"""
+    if o is None:
+        return U * (cnt - 1).clamp_min(0) * a
+    return U * cnt * (a + o.abs())
+
+
+def pad_bwd(dpad, hw, pads, mode, din0=None):
+    """vts_pad_bwd: din (+)= the adjoint of the padding's index map applied to dpad: every source pixel sums the padded positions that read it"""
+    h, w = hw
+    pt, pb, pl, pr = pads
+    g = _f64(dpad)
+    sy, sx = pad_index(h, pt, pb, mode), pad_index(w, pl, pr, mode)
+    ref, a = _scatter2(g, sy, sx, h, w), _scatter2(g.abs(), sy, sx, h, w)
+    cnt = _scatter2(torch.ones(g.shape[-2:], dtype=torch.float64), sy, sx, h, w)
+    o = _f64(din0)
+    return {"din": (ref if o is None else ref + o, _sum_unit(cnt, a, o))}
+
+
+def _axis_down(size):
+    """(taps, paths) [OH, H] of one axis of Downsample: reflect pad 1, [1 2 1] / 4, stride 2"""
+    o = (size - 1) // 2 + 1
+    src = pad_index(size, 1, 1, 1)                  # positions -1 .. size
+    A, P = torch.zeros(o, size, dtype=torch.float64), torch.zeros(o, size, dtype=torch.float64)
+    for y in range(o):
+        for i, f in enumerate((0.25, 0.5, 0.25)):
+            s = int(src[2 * y + i])
+            A[y, s] += f
+            P[y, s] += 1
+    return A, P
+
+
+def _axis_up(size):
+    """(taps, paths) [2 H, H] of one axis of Upsample: out[y] = sum_u P[u] f[y + 3 - 2 u], P = replicate pad 1, f = [1 3 3 1] / 4"""
+    f = (0.25, 0.75, 0.75, 0.25)
+    A, P = torch.zeros(2 * size, size, dtype=torch.float64), torch.zeros(2 * size, size, dtype=torch.float64)
+    for y in range(2 * size):
+        for u in range(size + 2):
+            k = y + 3 - 2 * u
+            if 0 <= k <= 3:
+                s = min(max(u - 1, 0), size - 1)
+                A[y, s] += f[k]
+                P[y, s] += 1
+    return A, P
+
+
+def _sep(Ay, Ax, x):
+    return torch.einsum("oh,nchw,pw->ncop", Ay, x, Ax)
+
+
+def _blur(axis, x, scale, shift, act, K):
+    assert act != 3
+    v, a, r = affine_act(x, scale, shift, act)
+    h, w = v.shape[-2:]
+    (Ay, _), (Ax, _) = axis(h), axis(w)
+    return {"out": (_sep(Ay, Ax, v), U * (float(r.max()) + K) * _sep(Ay, Ax, a))}
+
+
+def _blur_bwd(axis, dout, hw, din0):
+    g = _f64(dout)
+    (Ay, Py), (Ax, Px) = axis(hw[0]), axis(hw[1])
+    ref, a = _sep(Ay.t(), Ax.t(), g), _sep(Ay.t(), Ax.t(), g.abs())
+    K = Py.sum(0)[:, None] * Px.sum(0)[None, :]              # products summed into the element (paths, before the reflection folds them)
+    o = _f64(din0)
+    if o is None:
+        return {"din": (ref, U * K * a)}
+    return {"din": (ref + o, U * (K + 1) * (a + o.abs()))}
+
+
+def blur_down(x, scale=None, shift=None, act=0):
+    """vts_blur_down: reflect pad 1, depthwise [1 2 1] x [1 2 1] / 16, stride 2, of act(x * scale + shift): K = 9 products"""
+    return _blur(_axis_down, x, scale, shift, act, 9)
+
+
+def blur_down_bwd(dout, hw, din0=None):
+    return _blur_bwd(_axis_down, dout, hw, din0)
+
+
+def blur_up(x, scale=None, shift=None, act=0):
+    """vts_blur_up: replicate pad 1, depthwise transposed [1 3 3 1] x [1 3 3 1] * 4 / 64, stride 2, cropped to 2H x 2W: K = 4 products"""
+    return _blur(_axis_up, x, scale, shift, act, 4)
+
+
+def blur_up_bwd(dout, hw, din0=None):
+    return _blur_bwd(_axis_up, dout, hw, din0)
+
+
+def tap_embed(w, K, oy, ox):
+    """vts_tap_embed(_at): w4[r, i, j] = w[r, oy + i, ox + j] inside the K x K grid, 0 outside (exact: compare bitwise).  -> [rows, 4, 4]"""
+    w = w.reshape(-1, K, K)
+    out = torch.zeros(w.shape[0], 4, 4, dtype=w.dtype)
+    for i in range(4):
+        for j in range(4):
+            if 0 <= oy + i < K and 0 <= ox + j < K:
+                out[:, i, j] = w[:, oy + i, ox + j]
+    return out
+
+
+def tap_extract(dw4, K, oy, ox, dw0=None):
+    """vts_tap_extract(_at): dw[r, oy + i, ox + j] (+)= dw4[r, i, j] inside the K x K grid -> (ref [rows, K, K] with zeros (dw0 given: dw0)
+    outside the block, unit, bool mask [K, K] of the elements the call owns)"""
+    g = _f64(dw4).reshape(-1, 4, 4)
+    ref = torch.zeros(g.shape[0], K, K, dtype=torch.float64) if dw0 is None else _f64(dw0).reshape(-1, K, K).clone()
+    unit, own = torch.zeros_like(ref), torch.zeros(K, K, dtype=torch.bool)
+    for i in range(4):
+        for j in range(4):
+            ky, kx = oy + i, ox + j
+            if 0 <= ky < K and 0 <= kx < K:
+                own[ky, kx] = True
+                if dw0 is not None:
+                    unit[:, ky, kx] = U * (ref[:, ky, kx].abs() + g[:, i, j].abs())
+                    ref[:, ky, kx] += g[:, i, j]
+                else:
+                    ref[:, ky, kx] = g[:, i, j]
+    return {"dw": (ref, unit), "own": own}
+
+
+def table_matrix(mins, sizes, w, n_in):
+    """the table of one axis (first index, window length, weights [n_out, K]) as a dense [n_out, n_in] float64 matrix"""
+    mins, sizes, w = [torch.as_tensor(t) for t in (mins, sizes, w)]
+    m = torch.zeros(len(mins), n_in, dtype=torch.float64)
+    for o in range(len(mins)):
+        lo, k = int(mins[o]), int(sizes[o])
+        m[o, lo:lo + k] = w[o, :k].double()
+    return m
+
+
+def resample_table(x, ytab, xtab, out0=None):
+    """vts_resample_table: out[y, x] (+)= sum_j wy[y][j] sum_i wx[x][i] in[ymin[y] + j][xmin[x] + i], the given tables applied in float64.
+    K = ysize[y] * xsize[x] products; r = 1 for the row sum's own rounding on its way into the column sum (+ 1 for the accumulate)"""
+    x = _f64(x)
+    Wy, Wx = table_matrix(*ytab, x.shape[-2]), table_matrix(*xtab, x.shape[-1])
+    ref, a = _sep(Wy, Wx, x), _sep(Wy.abs(), Wx.abs(), x.abs())
+    K = torch.as_tensor(ytab[1]).double()[:, None] * torch.as_tensor(xtab[1]).double()[None, :]
+    o = _f64(out0)
+    if o is None:
+        return {"out": (ref, U * (K + 1) * a)}
+    return {"out": (ref + o, U * (K + 2) * (a + o.abs()))}
+
+
+def _ufd_axis(size, k, up, down, p0, p1):
+    """[k taps][n_out, size] 0 / 1 selection of one axis of upfirdn2d: tap t of output o reads position o * down + t - p0 of the
+    zero-inserted signal (sample i at i * up, length size * up), padded by (p0, p1) (negative: cropped)"""
+    n_out = (size * up + p0 + p1 - k) // down + 1
+    assert size * up + p0 + p1 >= k and n_out >= 1
+    S = torch.zeros(k, n_out, size, dtype=torch.float64)
+    for t in range(k):
+        for o in range(n_out):
+            pos = o * down + t - p0
+            if 0 <= pos < size * up and pos % up == 0:
+                S[t, o, pos // up] = 1
+    return S
+
+
+def upfirdn2d(x, kernel, up=1, down=1, padx=(0, 0), pady=(0, 0), out0=None):
+    """vts_upfirdn2d: zero-insertion upsampling by `up`, padding (negative = crop) per axis, correlation with the flipped kernel,
+    decimation by `down`.  K = the taps that meet a sample (not a padding or inserted zero)"""
+    x = _f64(x)
+    kf = torch.flip(_f64(kernel), [0, 1])
+    Sy, Sx = _ufd_axis(x.shape[-2], kf.shape[0], up, down, *pady), _ufd_axis(x.shape[-1], kf.shape[1], up, down, *padx)
+    ref = torch.einsum("ab,aoh,nchw,bpw->ncop", kf, Sy, x, Sx)
+    a = torch.einsum("ab,aoh,nchw,bpw->ncop", kf.abs(), Sy, x.abs(), Sx)
+    K = torch.einsum("aoh,bpw->op", Sy, Sx)
+    o = _f64(out0)
+    if o is None:
+        return {"out": (ref, U * K * a)}
+    return {"out": (ref + o, U * (K + 1) * (a + o.abs()))}
+
+
+def upfirdn2d_bwd(dout, hw, kernel, up=1, down=1, padx=(0, 0), pady=(0, 0), din0=None):
+    """vts_upfirdn2d_bwd: din (+)= the adjoint of upfirdn2d (input size hw) applied to dout"""
+    g = _f64(dout)
+    kf = torch.flip(_f64(kernel), [0, 1])
+    Sy, Sx = _ufd_axis(hw[0], kf.shape[0], up, down, *pady), _ufd_axis(hw[1], kf.shape[1], up, down, *padx)
+    assert g.shape[-2:] == (Sy.shape[1], Sx.shape[1])
+    ref = torch.einsum("ab,aoh,ncop,bpw->nchw", kf, Sy, g, Sx)
+    a = torch.einsum("ab,aoh,ncop,bpw->nchw", kf.abs(), Sy, g.abs(), Sx)
+    K = torch.einsum("aoh,bpw->hw", Sy, Sx)
+    o = _f64(din0)
+    if o is None:
+        return {"din": (ref, U * K * a)}
+    return {"din": (ref + o, U * (K + 1) * (a + o.abs()))}
+
+
+def _bias_v(x, bias):
+    x = _f64(x)
+    n, c = x.shape[:2]
+    shape = (1, c) + (1,) * (x.dim() - 2)
+    if bias is None:
+        return x, x.abs(), 0
+    b = _f64(bias).reshape(shape)
+    return x + b, x.abs() + b.abs(), 1
+
+
+def bias_act(x, bias, res, slope, gain):
+    """vts_bias_act: out = lrelu(x + bias, slope) * gain (+ res).  r: the bias add 1, the slope 1 where x + bias <= 0 (a slope of 0 is
+    exact), the gain 1 (a gain of 1 is exact), the residual add 1.  x + bias == 0 gives exactly 0 (+ res)."""
+    slope, gain = _f32(slope), _f32(gain)
+    v, a, r = _bias_v(x, bias)
+    neg = ~(v > 0)
+    f = torch.where(neg, torch.full_like(v, slope), torch.ones_like(v)) * gain
+    r = r + (neg.double() if slope != 0.0 else 0.0) + (1 if gain != 1.0 else 0)
+    ref, a = v * f, a * f.abs()
+    if res is not None:
+        o = _f64(res)
+        ref, a, r = ref + o, a + o.abs(), r + 1
+    return {"out": (ref, U * r * a)}
+
+
+def bias_act_bwd(g, x, bias, slope, gain):
+    """vts_bias_act_bwd: dx = g * gain * (x + bias > 0 ? 1 : slope): the gain 1, the slope 1 on its branch (x + bias == 0 takes it)"""
+    slope, gain = _f32(slope), _f32(gain)
+    v, _, _ = _bias_v(x, bias)
+    g = _f64(g)
+    neg = ~(v > 0)
+    f = torch.where(neg, torch.full_like(v, slope), torch.ones_like(v)) * gain
+    r = (1 if gain != 1.0 else 0) + (neg.double() if slope != 0.0 else 0.0)
+    return {"dx": (g * f, U * r * (g * f).abs())}
+
+
+def nearest_index(n_in, n_out):
+    """source index of every output position under F.interpolate(mode="nearest") on the CPU (ATen's float rule) -> int64 [n_out]"""
+    src = torch.arange(n_in, dtype=torch.float32).view(1, 1, n_in, 1)
+    return torch.nn.functional.interpolate(src, size=(n_out, 1), mode="nearest").view(n_out).long()
+
+
+def nearest_resize(x, size):
+    """vts_nearest_resize: a gather (exact: compare bitwise) -> the resized tensor in x's dtype"""
+    iy, ix = nearest_index(x.shape[-2], size[0]), nearest_index(x.shape[-1], size[1])
+    return x[..., iy, :][..., ix]
+
+
+def nearest_resize_bwd(dout, hw, din0=None):
+    """vts_nearest_resize_bwd: din (+)= the sum of the outputs that read the pixel (none: exactly 0)"""
+    g = _f64(dout)
+    iy, ix = nearest_index(hw[0], g.shape[-2]), nearest_index(hw[1], g.shape[-1])
+    ref, a = _scatter2(g, iy, ix, *hw), _scatter2(g.abs(), iy, ix, *hw)
+    cnt = _scatter2(torch.ones(g.shape[-2:], dtype=torch.float64), iy, ix, *hw)
+    o = _f64(din0)
+    return {"din": (ref if o is None else ref + o, _sum_unit(cnt, a, o))}
+
+
+def nearest_up2(x):
+    """vts_nearest_up2: every pixel written to its 2 x 2 cell (exact) -> in x's dtype"""
+    return x.repeat_interleave(2, -2).repeat_interleave(2, -1)
+
+
+def nearest_up2_bwd(dout, din0=None):
+    """vts_nearest_up2_bwd: din (+)= the sum of the 2 x 2 cell: 3 roundings (+ 1)"""
+    g = _f64(dout)
+    cell = lambda t: t[..., 0::2, 0::2] + t[..., 0::2, 1::2] + t[..., 1::2, 0::2] + t[..., 1::2, 1::2]
+    ref, a = cell(g), cell(g.abs())
+    o = _f64(din0)
+    if o is None:
+        return {"din": (ref, 3 * U * a)}
+    return {"din": (ref + o, 4 * U * (a + o.abs()))}
+
+
+def tanh_bwd(g, y):
+    """vts_tanh_bwd: dz = g (1 - y^2): the square, the subtraction, the product: 3 roundings of |g| (1 + y^2)"""
+    g, y = _f64(g), _f64(y)
+    return {"dz": (g * (1 - y * y), 3 * U * g.abs() * (1 + y * y))}

@@ -585,3 +585,287 @@ def test_sampler_and_staging_judges():
     imgs, store = rnd(g, 3, 4).float(), rnd(g, 2, 4).float()
     out, st = R.pool_query(imgs, store, torch.tensor([-1, 1, 1]), torch.tensor([1, 1, -1]))
     assert torch.equal(out[0], imgs[0]) and torch.equal(out[1], imgs[0]) and torch.equal(out[2], imgs[1]) and torch.equal(st[1], imgs[1])
+
+
+# ---- the padding / resampling / FIR judges (tests/test_resample_gpu.py) against independent float64 evaluations ------------------------
+import os  # noqa: E402
+import sys  # noqa: E402
+
+from oracle import stylegan2 as sg2  # noqa: E402
+
+PAD_MODE = {0: "constant", 1: "reflect", 2: "replicate"}
+SLOPE32 = float(torch.tensor(0.2, dtype=torch.float32))
+
+
+def act32(v, a):
+    return {0: v, 1: F.leaky_relu(v, SLOPE32), 2: F.relu(v), 3: torch.tanh(v)}[a]
+
+
+def refuses(ref, unit, border=True):
+    """the two planted errors the judge must refuse: a border element taken from the neighbouring pixel, and one element off by 4 units"""
+    ref, unit = ref.clone(), unit.clone()
+    if border and ref.shape[-1] > 1:
+        got = ref.clone()
+        flat = (ref[..., 0, 0] - ref[..., 0, 1]).abs().reshape(-1)
+        j = int(torch.argmax(flat))                       # the plane where the two pixels differ most
+        got.reshape(-1, *ref.shape[-2:])[j, 0, 0] = ref.reshape(-1, *ref.shape[-2:])[j, 0, 1]
+        assert float(flat[j]) > 0 and R.worst(got, ref, unit)[0] > 1.01
+    i = int(torch.argmax(unit.reshape(-1)))
+    got = ref.clone().reshape(-1)
+    if float(unit.reshape(-1)[i]) > 0:
+        got[i] += 4 * unit.reshape(-1)[i]
+        ratio, at = R.worst(got, ref, unit)
+        assert at == i and 3.9 < ratio < 4.1
+    else:                                                 # an exact judge: any change at all
+        got[i] = got[i] + 2.0 ** -20
+        assert R.worst(got, ref, unit)[0] == math.inf
+    assert R.worst(ref.clone(), ref, unit)[0] == 0
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2])
+@pytest.mark.parametrize("act_", [0, 1, 2, 3])
+@pytest.mark.parametrize("pads", [(3, 3, 3, 3), (2, 0, 1, 3), (0, 0, 0, 0), (4, 4, 6, 6)])
+def test_pad_judges_match_f_pad_and_its_autograd(mode, act_, pads):
+    if mode != 1 and pads == (4, 4, 6, 6):
+        pads = (5, 6, 8, 9)                               # beyond the image: legal for zero and replicate
+    g = torch.Generator().manual_seed(mode * 16 + act_ * 4 + pads[0])
+    n, c, h, w = 2, 3, 5, 7
+    pt, pb, pl, pr = pads
+    x, sc, sh = rnd(g, n, c, h, w), rnd(g, n, c), rnd(g, n, c) * 0.3
+    res = rnd(g, n, c, h + pt + pb, w + pl + pr)
+    for aff in (True, False):
+        for r in (None, res):
+            v = act32(x * sc[:, :, None, None] + sh[:, :, None, None] if aff else x, act_)
+            want = F.pad(v, (pl, pr, pt, pb), mode=PAD_MODE[mode]) + (0 if r is None else r)
+            ref, unit = R.pad_affine(x, sc if aff else None, sh if aff else None, pads, mode, act_, r)["out"]
+            assert close(ref, want)
+            if aff or act_ in (1, 3) or r is not None:
+                refuses(ref, unit, border=mode == 1 and sum(pads) > 0)
+            else:
+                assert float(unit.max()) == 0             # a gather: exact
+    dpad = rnd(g, n, c, h + pt + pb, w + pl + pr)
+    xg = x.clone().requires_grad_(True)
+    (F.pad(xg, (pl, pr, pt, pb), mode=PAD_MODE[mode]) * dpad).sum().backward()
+    din0 = rnd(g, n, c, h, w)
+    assert close(R.pad_bwd(dpad, (h, w), pads, mode)["din"][0], xg.grad)
+    ref, unit = R.pad_bwd(dpad, (h, w), pads, mode, din0)["din"]
+    assert close(ref, xg.grad + din0)
+    refuses(ref, unit)
+
+
+def test_pad_judge_sizes_one_and_the_tanh_unit():
+    g = torch.Generator().manual_seed(3)
+    x = rnd(g, 1, 1, 1, 1)
+    for mode in (0, 2):
+        assert close(R.pad_affine(x, None, None, (2, 1, 1, 2), mode, 0)["out"][0], F.pad(x, (1, 2, 2, 1), mode=PAD_MODE[mode]))
+    # tanh: the argument's rounding u |t| (1 - ref^2) plus E u |ref|; without an affine the argument is exact
+    x, sc, sh = torch.tensor([[[[2.0]]]], dtype=D64), torch.tensor([[1.5]], dtype=D64), torch.tensor([[-0.5]], dtype=D64)
+    ref, unit = R.pad_affine(x, sc, sh, (0, 0, 0, 0), 0, 3)["out"]
+    t = math.tanh(2.5)
+    assert close(ref, torch.tensor(t, dtype=D64)) and abs(float(unit) - R.U * (3.5 * (1 - t * t) + R.TANH_E * t)) < 1e-20
+    assert abs(float(R.pad_affine(x, None, None, (0, 0, 0, 0), 0, 3)["out"][1]) - R.U * R.TANH_E * math.tanh(2.0)) < 1e-20
+    assert R.TANH_E == 2 * R.TANH_E_MEASURED + 2
+
+
+@pytest.mark.parametrize("hw", [(2, 2), (3, 2), (5, 7), (8, 130), (9, 129)])
+def test_blur_down_judges_match_the_oracle_and_its_autograd(hw):
+    g = torch.Generator().manual_seed(hw[0] * 7 + hw[1])
+    x, sc, sh = rnd(g, 2, 3, *hw), rnd(g, 2, 3), rnd(g, 2, 3) * 0.3
+    for a in (0, 1, 2):
+        ref, unit = R.blur_down(x, sc, sh, a)["out"]
+        assert close(ref, nets.blur_down(act32(x * sc[:, :, None, None] + sh[:, :, None, None], a)))
+        refuses(ref, unit)
+    assert close(R.blur_down(x)["out"][0], nets.blur_down(x))
+    xg = x.clone().requires_grad_(True)
+    y = nets.blur_down(xg)
+    dy, d0 = rnd(g, *y.shape), rnd(g, *x.shape)
+    (y * dy).sum().backward()
+    assert close(R.blur_down_bwd(dy, hw)["din"][0], xg.grad)
+    ref, unit = R.blur_down_bwd(dy, hw, d0)["din"]
+    assert close(ref, xg.grad + d0)
+    refuses(ref, unit)
+
+
+@pytest.mark.parametrize("hw", [(1, 1), (1, 3), (5, 33), (3, 64)])
+def test_blur_up_judges_match_the_oracle_and_its_autograd(hw):
+    g = torch.Generator().manual_seed(hw[0] * 7 + hw[1])
+    x, sc, sh = rnd(g, 2, 3, *hw), rnd(g, 2, 3), rnd(g, 2, 3) * 0.3
+    for a in (0, 1, 2):
+        ref, unit = R.blur_up(x, sc, sh, a)["out"]
+        assert close(ref, nets.blur_up(act32(x * sc[:, :, None, None] + sh[:, :, None, None], a)))
+        refuses(ref, unit, border=hw != (1, 1))
+    xg = x.clone().requires_grad_(True)
+    y = nets.blur_up(xg)
+    dy, d0 = rnd(g, *y.shape), rnd(g, *x.shape)
+    (y * dy).sum().backward()
+    assert close(R.blur_up_bwd(dy, hw)["din"][0], xg.grad)
+    ref, unit = R.blur_up_bwd(dy, hw, d0)["din"]
+    assert close(ref, xg.grad + d0)
+    refuses(ref, unit, border=hw[1] > 1)
+
+
+@pytest.mark.parametrize("K", [1, 3, 5, 7, 8])
+@pytest.mark.parametrize("origin", [(0, 0), (4, 0), (0, 4), (4, 4), (-3, -3), (-1, 0), (7, 7)])
+def test_tap_judges_match_a_slice_of_the_zero_extended_grid(K, origin):
+    g = torch.Generator().manual_seed(K)
+    oy, ox = origin
+    w = rnd(g, 17, K, K).requires_grad_(True)
+    block = F.pad(w, (3, 11 - K, 3, 11 - K))[:, oy + 3:oy + 7, ox + 3:ox + 7]
+    assert torch.equal(R.tap_embed(w.detach(), K, oy, ox), block.detach())
+    dw4, dw0 = rnd(g, 17, 4, 4), rnd(g, 17, K, K)
+    (block * dw4).sum().backward()
+    res = R.tap_extract(dw4, K, oy, ox)
+    own = torch.zeros(K, K, dtype=torch.bool)
+    own[max(oy, 0):max(min(oy + 4, K), 0), max(ox, 0):max(min(ox + 4, K), 0)] = True
+    assert torch.equal(res["own"], own) and torch.equal(res["dw"][0], w.grad) and bool((w.grad[:, ~own] == 0).all())
+    acc = R.tap_extract(dw4, K, oy, ox, dw0)["dw"]
+    assert close(acc[0], dw0 + w.grad) and bool((acc[1][:, ~own] == 0).all()) and torch.equal(acc[0][:, ~own], dw0[:, ~own])
+    if bool(own.any()):
+        refuses(acc[0], acc[1], border=False)
+
+
+@pytest.mark.parametrize("geom", [(32, 32, 64, 64), (37, 53, 32, 32), (96, 80, 24, 20), (32, 32, 32, 32), (5, 300, 3, 7)])
+def test_resample_table_judge_applies_the_host_built_tables(geom):
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "visual-tactile-synthesis_amd"))
+    from vts import ops
+    ih, iw, oh, ow = geom
+    g = torch.Generator().manual_seed(ih + oh)
+    x, o0 = rnd(g, 1, 2, ih, iw), rnd(g, 1, 2, oh, ow)
+    ay, ax = ops._aa_axis(ih, oh), ops._aa_axis(iw, ow)
+    ref, unit = R.resample_table(x, ay, ax)["out"]
+    # a direct table product, element by element
+    want = torch.zeros(1, 2, oh, ow, dtype=D64)
+    for y in range(oh):
+        for xx in range(ow):
+            win = x[:, :, ay[0][y]:ay[0][y] + ay[1][y], ax[0][xx]:ax[0][xx] + ax[1][xx]]
+            wy, wx = torch.from_numpy(ay[2][y, :ay[1][y]]).double(), torch.from_numpy(ax[2][xx, :ax[1][xx]]).double()
+            want[:, :, y, xx] = torch.einsum("ncji,j,i->nc", win, wy, wx)
+    assert close(ref, want)
+    k = int(ay[1][1]) * int(ax[1][2])                     # K = ysize * xsize, r = 1
+    absref = torch.einsum("oh,hw,pw->op", R.table_matrix(*ay, ih).abs(), x[0, 0].abs(), R.table_matrix(*ax, iw).abs())[1, 2]
+    assert abs(float(unit[0, 0, 1, 2]) / (R.U * (k + 1) * float(absref)) - 1) < 1e-12
+    # ... which is PyTorch's anti-aliased bicubic up to the tables' fp32 weights
+    assert float((ref - F.interpolate(x, (oh, ow), mode="bicubic", align_corners=False, antialias=True)).abs().max()) < 5e-6
+    if (ih, iw) == (oh, ow):
+        assert torch.equal(ref, x)
+    refuses(ref, unit)
+    acc = R.resample_table(x, ay, ax, o0)["out"]
+    assert close(acc[0], want + o0) and bool((acc[1] > unit).all())
+    # the adjoint through the transposed tables is autograd's
+    xg = x.clone().requires_grad_(True)
+    (torch.einsum("oh,nchw,pw->ncop", R.table_matrix(*ay, ih), xg, R.table_matrix(*ax, iw)) * o0).sum().backward()
+    adj, aunit = R.resample_table(o0, ops._aa_transpose(*ay, ih), ops._aa_transpose(*ax, iw))["out"]
+    assert close(adj, xg.grad)
+    refuses(adj, aunit)
+
+
+UFD_CASES = [  # kernel shape or taps, up, down, padx, pady, H, W
+    ((1, 3, 3, 1), 1, 1, (2, 1), (2, 1), 9, 11), ((1, 3, 3, 1), 1, 1, (1, 1), (1, 1), 17, 65), ((1, 3, 3, 1), 2, 1, (2, 1), (2, 1), 5, 7),
+    ((1, 3, 3, 1), 1, 2, (1, 1), (1, 1), 9, 12), ((1, 3, 3, 1), 2, 2, (2, 1), (2, 1), 7, 6), ((1, 3, 3, 1), 1, 1, (-1, 2), (-1, 2), 8, 9),
+    ((1,), 1, 1, (0, 0), (0, 0), 4, 5), ((2, 3), 1, 1, (1, 2), (0, 1), 6, 7), ((9, 7), 1, 1, (3, 3), (4, 4), 6, 10), ((2, 3), 3, 2, (2, -1), (-2, 4), 6, 7),
+]
+
+
+def ufd_by_definition(x, k, up, down, padx, pady):
+    """zero insertion, F.pad with negative pads as crops, conv2d with the flipped kernel, decimation"""
+    n, c, h, w = x.shape
+    u = x.new_zeros(n, c, h * up, w * up)
+    u[:, :, ::up, ::up] = x
+    p = F.pad(u, (padx[0], padx[1], pady[0], pady[1]))
+    y = F.conv2d(p.reshape(n * c, 1, *p.shape[-2:]), torch.flip(k, [0, 1])[None, None])
+    return y.reshape(n, c, *y.shape[-2:])[:, :, ::down, ::down]
+
+
+@pytest.mark.parametrize("case", UFD_CASES)
+def test_upfirdn2d_judges_match_the_definition_the_oracle_and_autograd(case):
+    taps, up, down, padx, pady, h, w = case
+    g = torch.Generator().manual_seed(h * 31 + w)
+    k = sg2.make_kernel(taps).double() * up * up if len(taps) != 2 else rnd(g, *taps)
+    x = rnd(g, 2, 3, h, w).requires_grad_(True)
+    want = ufd_by_definition(x, k, up, down, padx, pady)
+    ref, unit = R.upfirdn2d(x, k, up, down, padx, pady)["out"]
+    assert ref.shape == want.shape and close(ref, want.detach())
+    if padx == pady:
+        assert close(ref, sg2.upfirdn2d(x.detach(), k, up, down, padx))
+    refuses(ref, unit)
+    dy, o0, d0 = rnd(g, *want.shape), rnd(g, *want.shape), rnd(g, 2, 3, h, w)
+    (want * dy).sum().backward()
+    acc = R.upfirdn2d(x, k, up, down, padx, pady, o0)["out"]
+    assert close(acc[0], want.detach() + o0) and bool((acc[1] >= unit).all())
+    assert close(R.upfirdn2d_bwd(dy, (h, w), k, up, down, padx, pady)["din"][0], x.grad)
+    ref, unit = R.upfirdn2d_bwd(dy, (h, w), k, up, down, padx, pady, d0)["din"]
+    assert close(ref, x.grad + d0)
+    refuses(ref, unit)
+
+
+def test_upfirdn2d_unit_counts_only_the_taps_that_meet_a_sample():
+    k = sg2.make_kernel((1, 3, 3, 1)).double()
+    x = torch.ones(1, 1, 4, 4, dtype=D64)
+    ref, unit = R.upfirdn2d(x, k, 1, 1, (2, 1), (2, 1))["out"]
+    assert abs(float(unit[0, 0, 0, 0]) - R.U * 4 * float(ref[0, 0, 0, 0])) < 1e-22 and abs(float(unit[0, 0, 2, 2]) - R.U * 16) < 1e-22
+    ref, unit = R.upfirdn2d(x, k, 1, 1, (5, 5), (0, 0))["out"]                 # outputs that see padding only: exactly 0
+    assert float(ref[0, 0, 0, 0]) == 0 and float(unit[0, 0, 0, 0]) == 0 and float(unit[0, 0, 0, 4]) > 0
+
+
+@pytest.mark.parametrize("sg", [(0.2, math.sqrt(2.0)), (0.2, 0.7), (0.0, 1.0)])
+@pytest.mark.parametrize("shape", [(1, 1, 1), (2, 3, 99)])
+def test_bias_act_judges_match_the_fused_leaky_relu_and_autograd(sg, shape):
+    g = torch.Generator().manual_seed(shape[2])
+    s32, g32 = R._f32(sg[0]), R._f32(sg[1])
+    x, b, res, dy = rnd(g, *shape), rnd(g, shape[1]), rnd(g, *shape), rnd(g, *shape)
+    x[:, :, ::7] = -b[None, :, None]                                            # exact ties
+    for bias in (b, None):
+        for r in (res, None):
+            xg = x.clone().requires_grad_(True)
+            y = F.leaky_relu(xg + (0 if bias is None else bias[None, :, None]), s32) * g32
+            ref, unit = R.bias_act(x, bias, r, *sg)["out"]
+            assert close(ref, y.detach() + (0 if r is None else r))
+            if bias is not None:
+                assert bool((ref[:, :, ::7] == (0 if r is None else r[:, :, ::7])).all())
+                assert close(ref, sg2.fused_leaky_relu(x, bias, s32, g32) + (0 if r is None else r))
+            if float(unit.max()) > 0:
+                refuses(ref, unit, border=False)
+            (y * dy).sum().backward()
+            ref, unit = R.bias_act_bwd(dy, x, bias, *sg)["dx"]
+            assert close(ref, xg.grad)                                          # autograd takes the slope branch at 0 as well
+            if bias is not None:
+                assert close(ref[:, :, ::7], dy[:, :, ::7] * s32 * g32)
+            if float(unit.max()) > 0:
+                refuses(ref, unit, border=False)
+    assert float(R.bias_act(x, None, None, 0.0, 1.0)["out"][1].max()) == 0       # ReLU without bias, gain or residual: exact
+
+
+@pytest.mark.parametrize("geom", [(14, 6, 46, 74), (9, 3, 111, 123), (46, 74, 14, 6), (7, 9, 7, 9), (5, 6, 10, 12), (30, 20, 4, 6)])
+def test_nearest_judges_match_f_interpolate_and_its_autograd(geom):
+    ih, iw, oh, ow = geom
+    g = torch.Generator().manual_seed(ih + ow)
+    x32 = torch.randn(2, 3, ih, iw, generator=g)
+    assert torch.equal(R.nearest_resize(x32, (oh, ow)), F.interpolate(x32, (oh, ow), mode="nearest"))
+    x = x32.double().requires_grad_(True)
+    dy, d0 = rnd(g, 2, 3, oh, ow), rnd(g, 2, 3, ih, iw)
+    (F.interpolate(x, (oh, ow), mode="nearest") * dy).sum().backward()
+    assert close(R.nearest_resize_bwd(dy, (ih, iw))["din"][0], x.grad)
+    ref, unit = R.nearest_resize_bwd(dy, (ih, iw), d0)["din"]
+    assert close(ref, x.grad + d0)
+    refuses(ref, unit)
+    if geom == (30, 20, 4, 6):
+        plain = R.nearest_resize_bwd(dy, (ih, iw))["din"]
+        assert int((plain[0][0, 0] == 0).sum()) == ih * iw - oh * ow and bool((plain[1][plain[0] == 0] == 0).all())
+
+
+def test_up2_and_tanh_bwd_judges_match_autograd():
+    g = torch.Generator().manual_seed(12)
+    x32 = torch.randn(1, 7, 3, 5, generator=g)
+    assert torch.equal(R.nearest_up2(x32), F.interpolate(x32, scale_factor=2, mode="nearest"))
+    x = x32.double().requires_grad_(True)
+    dy, d0 = rnd(g, 1, 7, 6, 10), rnd(g, 1, 7, 3, 5)
+    (F.interpolate(x, scale_factor=2, mode="nearest") * dy).sum().backward()
+    ref, unit = R.nearest_up2_bwd(dy, d0)["din"]
+    assert close(ref, x.grad + d0) and close(R.nearest_up2_bwd(dy)["din"][0], x.grad)
+    refuses(ref, unit)
+    z = rnd(g, 257).requires_grad_(True)
+    y, gz = torch.tanh(z), rnd(g, 257)
+    (y * gz).sum().backward()
+    ref, unit = R.tanh_bwd(gz, y.detach())["dz"]
+    assert close(ref, z.grad) and close(unit, 3 * R.U * gz.abs() * (1 + y.detach() ** 2))
+    refuses(ref.view(1, 257), unit.view(1, 257), border=False)

@@ -1,0 +1,186 @@
+"""The case table of tests/test_resample_gpu.py against csrc/vts_resample.hip, csrc/vts_stylegan2.hip and csrc/vts_spade.hip: every
+__global__ kernel and every instance string those files pass to vts_set_kernel is claimed by a row or named in COVERED_ELSEWHERE (a new
+kernel or dispatch alternative needs a new row), no row claims an instance the sources do not name, no row's input lies within KINK of a
+kink of its formula apart from the planted exact ties, the bitwise rows' float64 references are representable in fp32, and the nearest size
+pairs are pairs at which ATen's float rule and integer division disagree."""
+import os
+import re
+
+import torch
+
+import resample_cases as T
+from oracle import launch_ref as R
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "visual-tactile-synthesis_amd", "csrc")
+FILES = ("vts_resample.hip", "vts_stylegan2.hip", "vts_spade.hip")
+# the C entries whose launches the table judges: each must name its instance
+ENTRIES = ["vts_pad_affine", "vts_pad_bwd", "vts_blur_down", "vts_blur_down_bwd", "vts_blur_up", "vts_blur_up_bwd", "vts_tap_embed", "vts_tap_embed_at",
+           "vts_tap_extract", "vts_tap_extract_at", "vts_resample_table", "vts_upfirdn2d", "vts_upfirdn2d_bwd", "vts_bias_act", "vts_bias_act_bwd",
+           "vts_nearest_resize", "vts_nearest_resize_bwd", "vts_nearest_up2", "vts_nearest_up2_bwd", "vts_tanh_bwd"]
+
+
+def source():
+    out = ""
+    for name in FILES:
+        with open(os.path.join(CSRC, name)) as f:
+            out += f.read()
+    return out
+
+
+def global_kernels():
+    return sorted(set(re.findall(r"__global__\s+(?:__launch_bounds__\(\d+\)\s+)?void\s+(\w+)\s*\(", source())))
+
+
+def instance_strings(text=None):
+    out = []
+    for call in re.findall(r"\bvts_set_kernel\(([^;]*)\);", source() if text is None else text):
+        found = re.findall(r'"([^"]*)"', call)
+        assert found, call
+        out += found
+    return sorted(set(out))
+
+
+def entry_body(name):
+    m = re.search(r'extern "C" int %s\(.*?\n}\n' % name, source(), re.S)
+    assert m, name
+    return m.group(0)
+
+
+def kernels_of(instance):
+    """the kernel names an instance string is made of: 'ufd_tile_kernel adjoint'"""
+    return [re.sub(r" adjoint$", "", part) for part in instance.split("+")]
+
+
+def test_the_sources_are_read_as_expected():
+    k, s = global_kernels(), instance_strings()
+    assert len(k) >= 40 and "ufd_tile_kernel" in k and "nearest_up2_bwd_kernel" in k and "resample_table_kernel" in k and "sn_v_kernel" in k, k
+    assert "ufd_tile_kernel adjoint" in s and "pad_affine_kernel" in s and "tanh_bwd_kernel" in s, s
+
+
+def test_every_listed_entry_names_its_instance():
+    for name in ENTRIES:
+        named = instance_strings(entry_body(name))
+        assert named, "%s does not call vts_set_kernel" % name
+        assert set(named) <= T.claimed_instances(), (name, named)
+
+
+def test_every_kernel_and_instance_of_the_sources_is_claimed_by_a_row():
+    claimed = T.claimed_instances() | set(T.COVERED_ELSEWHERE)
+    unclaimed = [s for s in instance_strings() if s not in claimed]
+    assert not unclaimed, "instances without a row in tests/resample_cases.py: %s" % unclaimed
+    names = {k for c in claimed for k in kernels_of(c)}
+    missing = [k for k in global_kernels() if k not in names]
+    assert not missing, "__global__ kernels without a row in tests/resample_cases.py: %s" % missing
+
+
+def test_every_row_claims_an_instance_the_sources_name():
+    named = set(instance_strings())
+    unknown = [c for c in T.claimed_instances() if c not in named]
+    assert not unknown, unknown
+    assert set(T.COVERED_ELSEWHERE) <= set(global_kernels())
+    for path in set(T.COVERED_ELSEWHERE.values()):
+        assert os.path.exists(os.path.join(os.path.dirname(CSRC), "..", path)), path
+
+
+def test_dispatch_alternatives_are_both_claimed():
+    c = T.claimed_instances()
+    for pair in ((T.TILE, T.GEN), (T.TILE_ADJ, T.GEN_ADJ)):
+        assert set(pair) <= c, pair
+    fwd = {r[10] for r in T.UFD}
+    assert fwd == {T.TILE, T.GEN}
+    # both sides of each threshold: K = 8 | 9 x 7, NC = 6 | 65536, up = down = 1 | 2
+    gen = [r for r in T.UFD if r[10] == T.GEN]
+    assert any(r[4] == "k8" and r[10] == T.TILE for r in T.UFD) and any(r[4] == "k9x7" for r in gen) and any(r[1] > 65535 for r in gen)
+    assert any(r[5] == 2 and r[6] == 1 for r in gen) and any(r[5] == 1 and r[6] == 2 for r in gen) and any(r[5] == 2 and r[6] == 2 for r in gen)
+    # the grid-stride kernels' second sweep
+    assert any(r[1] * r[4] * r[5] > T.SECOND_SWEEP for r in T.NEAREST) and any(r[1] * r[2] * r[3] > T.SECOND_SWEEP for r in T.NEAREST)
+    assert any(r[1] * r[2] * r[3] > T.SECOND_SWEEP for r in T.UP2) and max(T.TANH_BWD) > T.SECOND_SWEEP
+
+
+def test_row_ids_are_unique():
+    ids = T.row_ids()
+    assert len(ids) == len(set(ids))
+
+
+def test_no_input_lies_near_a_kink_except_the_planted_ties():
+    rows = T.kink_rows()
+    assert len(rows) >= len(T.BIAS_ACT) + 16
+    ties = 0
+    for rid, d, tie in rows:
+        assert (d[tie] == 0).all(), "%s: a planted tie is not exact" % rid
+        rest = d[~tie]
+        assert (rest >= T.KINK).all(), "%s: %d elements within %g of a kink (closest %g)" % (rid, int((rest < T.KINK).sum()), T.KINK, float(rest.min()))
+        ties += int(tie.sum())
+    assert ties > len(T.BIAS_ACT)
+
+
+def test_the_kink_check_sees_a_violation():
+    sc, sh = T.affine(2, 3, 1)
+    x = ((1e-4 - sh.double()) / sc.double()).float().view(2, 3, 1, 1)         # fmaf(x, scale, shift) = 1e-4
+    assert float(T._kink_distance(x, sc, sh).max()) < T.KINK
+    assert float(T._kink_distance(T.off_kink(x, sc, sh), sc, sh).min()) >= 2 * T.KINK
+
+
+def _representable(rid, inputs, refs):
+    for t in inputs:
+        assert torch.equal(t, torch.round(t)) and float(t.abs().max()) <= 8, "%s: an input is not a small integer" % rid
+    for r in refs:
+        r = r.double()
+        assert torch.equal(r.float().double(), r), "%s: the float64 reference is not representable in fp32" % rid
+
+
+def test_bitwise_rows_have_integer_inputs_and_fp32_representable_references():
+    n = 0
+    for row in T.PAD_BWD:
+        dpad, seed = T.pad_bwd_inputs(row)
+        _representable(T.pad_bwd_id(row), [dpad, seed], [R.pad_bwd(dpad, row[2:4], row[4], row[5], s)["din"][0] for s in (None, seed)])
+        n += 1
+    for row in T.BLUR:
+        if row[6] in ("plain", "gap"):
+            x = T.blur_inputs(row)[0]
+            _representable(row[0], [x], [(R.blur_down if row[1] == "down" else R.blur_up)(x)["out"][0]])
+            n += 1
+    for row in T.BLUR_BWD:
+        g, seed = T.blur_bwd_inputs(row)
+        fn = R.blur_down_bwd if row[0] == "down" else R.blur_up_bwd
+        _representable("blur-%s-bwd-%dx%d" % row, [g, seed], [fn(g, row[1:], s)["din"][0] for s in (None, seed)])
+        n += 1
+    for row in T.TAP:
+        _representable(row[0], T.tap_inputs(row), [])
+        n += 1
+    for row in T.UFD:
+        if not row[9]:
+            continue
+        rid, nc, ih, iw, kname, up, down, padx, pady, _, _ = row
+        k = T.ufd_kernel(kname, up)
+        assert torch.equal(k * 64, torch.round(k * 64)), "%s: the taps are not multiples of 1 / 64" % rid
+        if nc > 64:
+            nc = 64               # the planes are independent draws of the same rule
+        oh, ow = T.ufd_out_hw(row)
+        x, g = T.ufd_input(row, (1, nc, ih, iw), "x"), T.ufd_input(row, (1, nc, oh, ow), "g")
+        so, si = T.ufd_input(row, (1, nc, oh, ow), "so"), T.ufd_input(row, (1, nc, ih, iw), "si")
+        _representable(rid, [x, g, so, si], [R.upfirdn2d(x, k, up, down, padx, pady, so)["out"][0], R.upfirdn2d_bwd(g, (ih, iw), k, up, down, padx, pady, si)["din"][0]])
+        n += 1
+    for row in T.NEAREST:
+        x, g, seed = T.nearest_inputs(row)
+        _representable(row[0], [x, g, seed], [R.nearest_resize_bwd(g, row[2:4], seed)["din"][0]])
+        n += 1
+    for row in T.UP2:
+        x, g, seed = T.up2_inputs(row)
+        _representable(row[0], [x, g, seed], [R.nearest_up2_bwd(g, seed)["din"][0]])
+        n += 1
+    assert n >= 100
+
+
+def test_the_nearest_pairs_are_pairs_where_the_float_rule_and_integer_division_differ():
+    for n_in, n_out in T.DIFFER:
+        assert T.rules_differ(n_in, n_out), (n_in, n_out)
+        # ... and ATen's CPU kernel follows the float rule there
+        import numpy as np
+        dst = np.arange(n_out)
+        f = np.minimum(np.floor(dst.astype(np.float32) * (np.float32(n_in) / np.float32(n_out))).astype(np.int64), n_in - 1)
+        assert R.nearest_index(n_in, n_out).tolist() == f.tolist()
+    assert not T.rules_differ(32, 16) and not T.rules_differ(7, 7) and not T.rules_differ(5, 10)
+    per_axis = {(r[2], r[4]) for r in T.NEAREST} | {(r[3], r[5]) for r in T.NEAREST}
+    assert set(T.DIFFER) <= per_axis
+    assert sum(T.rules_differ(a, b) for a in range(1, 130) for b in range(1, 130)) == 195

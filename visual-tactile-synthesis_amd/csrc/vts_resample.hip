@@ -227,15 +227,18 @@ extern "C" int vts_pad_affine(const vts_operand* in, int N, int H, int W, int pt
   PadK k{in->data, in->scale, in->shift, res, in->nstride, ons, in->C, H, W, pt, pl, H + pt + pb, W + pl + pr, mode, act, out};
   hipLaunchKernelGGL(pad_affine_kernel, dim3(cdiv(k.PW, 64), cdiv(k.PH, 4), N * in->C), dim3(256), 0, (hipStream_t)stream, k);
   VTS_CHECK_LAUNCH("vts_pad_affine");
+  vts_set_kernel("pad_affine_kernel");
   return VTS_OK;
 }
 
 extern "C" int vts_pad_bwd(const float* dpad, int N, int C, int H, int W, int pt, int pb, int pl, int pr, int mode, float* din,
                            int accumulate, void* stream) {
   VTS_CHECK_ARG(dpad && din && mode >= 0 && mode <= 2 && (int64_t)N * C <= 65535, "vts_pad_bwd: bad args");
+  VTS_CHECK_ARG(mode != 1 || (pt < H && pb < H && pl < W && pr < W), "vts_pad_bwd: reflect pad must be smaller than the image");
   PadBK k{dpad, C, H, W, pt, pb, pl, pr, H + pt + pb, W + pl + pr, mode, accumulate, din};
   hipLaunchKernelGGL(pad_bwd_kernel, dim3(cdiv(W, 64), cdiv(H, 4), N * C), dim3(256), 0, (hipStream_t)stream, k);
   VTS_CHECK_LAUNCH("vts_pad_bwd");
+  vts_set_kernel("pad_bwd_kernel");
   return VTS_OK;
 }
 
@@ -244,6 +247,7 @@ extern "C" int vts_blur_down(const vts_operand* in, int act, int N, int H, int W
   BlurK k{in->data, in->scale, in->shift, in->nstride, in->C, H, W, (H - 1) / 2 + 1, (W - 1) / 2 + 1, act, 0, out};
   hipLaunchKernelGGL(blur_down_kernel, dim3(cdiv(k.OW, 64), cdiv(k.OH, 4), N * in->C), dim3(256), 0, (hipStream_t)stream, k);
   VTS_CHECK_LAUNCH("vts_blur_down");
+  vts_set_kernel("blur_down_kernel");
   return VTS_OK;
 }
 
@@ -252,6 +256,7 @@ extern "C" int vts_blur_down_bwd(const float* dout, int N, int C, int H, int W, 
   BlurK k{dout, nullptr, nullptr, 0, C, H, W, (H - 1) / 2 + 1, (W - 1) / 2 + 1, 0, accumulate, din};
   hipLaunchKernelGGL(blur_down_bwd_kernel, dim3(cdiv(W, 64), cdiv(H, 4), N * C), dim3(256), 0, (hipStream_t)stream, k);
   VTS_CHECK_LAUNCH("vts_blur_down_bwd");
+  vts_set_kernel("blur_down_bwd_kernel");
   return VTS_OK;
 }
 
@@ -260,6 +265,7 @@ extern "C" int vts_blur_up(const vts_operand* in, int act, int N, int H, int W, 
   BlurK k{in->data, in->scale, in->shift, in->nstride, in->C, H, W, 2 * H, 2 * W, act, 0, out};
   hipLaunchKernelGGL(blur_up_kernel, dim3(cdiv(k.OW, 64), cdiv(k.OH, 4), N * in->C), dim3(256), 0, (hipStream_t)stream, k);
   VTS_CHECK_LAUNCH("vts_blur_up");
+  vts_set_kernel("blur_up_kernel");
   return VTS_OK;
 }
 
@@ -268,6 +274,7 @@ extern "C" int vts_blur_up_bwd(const float* dout, int N, int C, int H, int W, fl
   BlurK k{dout, nullptr, nullptr, 0, C, H, W, 2 * H, 2 * W, 0, accumulate, din};
   hipLaunchKernelGGL(blur_up_bwd_kernel, dim3(cdiv(W, 64), cdiv(H, 4), N * C), dim3(256), 0, (hipStream_t)stream, k);
   VTS_CHECK_LAUNCH("vts_blur_up_bwd");
+  vts_set_kernel("blur_up_bwd_kernel");
   return VTS_OK;
 }
 
@@ -275,6 +282,7 @@ extern "C" int vts_tap_embed(const float* w, int64_t rows, int K, int a, int b, 
   VTS_CHECK_ARG(w && w4 && rows >= 1 && K >= 1 && K <= 8 && a >= 0 && a <= 1 && b >= 0 && b <= 1, "vts_tap_embed: bad args");
   hipLaunchKernelGGL(tap_embed_kernel, dim3((unsigned)cdiv64(rows * 16, 256)), dim3(256), 0, (hipStream_t)stream, w, rows, K, 4 * a, 4 * b, w4);
   VTS_CHECK_LAUNCH("vts_tap_embed");
+  vts_set_kernel("tap_embed_kernel");
   return VTS_OK;
 }
 
@@ -283,6 +291,7 @@ extern "C" int vts_tap_extract(const float* dw4, int64_t rows, int K, int a, int
   hipLaunchKernelGGL(tap_extract_kernel, dim3((unsigned)cdiv64(rows * 16, 256)), dim3(256), 0, (hipStream_t)stream, dw4, rows, K, 4 * a, 4 * b, dw,
                      accumulate);
   VTS_CHECK_LAUNCH("vts_tap_extract");
+  vts_set_kernel("tap_extract_kernel");
   return VTS_OK;
 }
 
@@ -290,6 +299,7 @@ extern "C" int vts_tap_embed_at(const float* w, int64_t rows, int K, int oy, int
   VTS_CHECK_ARG(w && w4 && rows >= 1 && K >= 1 && K <= 8 && oy >= -3 && oy <= 7 && ox >= -3 && ox <= 7, "vts_tap_embed_at: bad args");
   hipLaunchKernelGGL(tap_embed_kernel, dim3((unsigned)cdiv64(rows * 16, 256)), dim3(256), 0, (hipStream_t)stream, w, rows, K, oy, ox, w4);
   VTS_CHECK_LAUNCH("vts_tap_embed_at");
+  vts_set_kernel("tap_embed_kernel");
   return VTS_OK;
 }
 
@@ -298,6 +308,7 @@ extern "C" int vts_tap_extract_at(const float* dw4, int64_t rows, int K, int oy,
   hipLaunchKernelGGL(tap_extract_kernel, dim3((unsigned)cdiv64(rows * 16, 256)), dim3(256), 0, (hipStream_t)stream, dw4, rows, K, oy, ox, dw,
                      accumulate);
   VTS_CHECK_LAUNCH("vts_tap_extract_at");
+  vts_set_kernel("tap_extract_kernel");
   return VTS_OK;
 }
 
@@ -339,5 +350,6 @@ extern "C" int vts_resample_table(const float* in, int64_t NC, int IH, int IW, c
   hipLaunchKernelGGL(resample_table_kernel, dim3((unsigned)cdiv64(NC * OH * OW, 256)), dim3(256), 0, (hipStream_t)stream, in, NC, IH, IW, ymin, ysize,
                      wy, KY, xmin, xsize, wx, KX, out, OH, OW, accumulate);
   VTS_CHECK_LAUNCH("vts_resample_table");
+  vts_set_kernel("resample_table_kernel");
   return VTS_OK;
 }

@@ -421,6 +421,7 @@ extern "C" int vts_tanh_bwd(const float* g, const float* y, int64_t n, float* dz
   VTS_CHECK_ARG(g && y && dz && n >= 1, "vts_tanh_bwd: bad args");
   hipLaunchKernelGGL(tanh_bwd_kernel, dim3(flat_grid(n)), dim3(256), 0, (hipStream_t)stream, g, y, n, dz);
   VTS_CHECK_LAUNCH("vts_tanh_bwd");
+  vts_set_kernel("tanh_bwd_kernel");
   return VTS_OK;
 }
 
@@ -429,6 +430,7 @@ extern "C" int vts_nearest_resize(const float* x, int64_t NC, int IH, int IW, in
   hipLaunchKernelGGL(nearest_fwd_kernel, dim3(flat_grid(NC * OH * OW)), dim3(256), 0, (hipStream_t)stream, x, NC, IH, IW, OH, OW, (float)IH / (float)OH,
                      (float)IW / (float)OW, out);
   VTS_CHECK_LAUNCH("vts_nearest_resize");
+  vts_set_kernel("nearest_fwd_kernel");
   return VTS_OK;
 }
 
@@ -437,20 +439,25 @@ extern "C" int vts_nearest_resize_bwd(const float* dout, int64_t NC, int IH, int
   hipLaunchKernelGGL(nearest_bwd_kernel, dim3(flat_grid(NC * IH * IW)), dim3(256), 0, (hipStream_t)stream, dout, NC, IH, IW, OH, OW,
                      (float)IH / (float)OH, (float)IW / (float)OW, din, accumulate);
   VTS_CHECK_LAUNCH("vts_nearest_resize_bwd");
+  vts_set_kernel("nearest_bwd_kernel");
   return VTS_OK;
 }
 
 extern "C" int vts_nearest_up2(const float* x, int64_t NC, int H, int W, float* out, void* stream) {
   VTS_CHECK_ARG(x && out && NC >= 1 && H >= 1 && W >= 1, "vts_nearest_up2: bad args");
+  VTS_CHECK_ARG(((uintptr_t)out & 7) == 0, "vts_nearest_up2: out must be 8-byte aligned (float2 stores)");
   hipLaunchKernelGGL(nearest_up2_kernel, dim3(flat_grid(NC * H * W)), dim3(256), 0, (hipStream_t)stream, x, NC, H, W, out);
   VTS_CHECK_LAUNCH("vts_nearest_up2");
+  vts_set_kernel("nearest_up2_kernel");
   return VTS_OK;
 }
 
 extern "C" int vts_nearest_up2_bwd(const float* dout, int64_t NC, int H, int W, float* din, int accumulate, void* stream) {
   VTS_CHECK_ARG(dout && din && NC >= 1 && H >= 1 && W >= 1, "vts_nearest_up2_bwd: bad args");
+  VTS_CHECK_ARG(((uintptr_t)dout & 7) == 0, "vts_nearest_up2_bwd: dout must be 8-byte aligned (float2 loads)");
   hipLaunchKernelGGL(nearest_up2_bwd_kernel, dim3(flat_grid(NC * H * W)), dim3(256), 0, (hipStream_t)stream, dout, NC, H, W, din, accumulate);
   VTS_CHECK_LAUNCH("vts_nearest_up2_bwd");
+  vts_set_kernel("nearest_up2_bwd_kernel");
   return VTS_OK;
 }
 

@@ -364,11 +364,13 @@ extern "C" int vts_upfirdn2d(const float* in, int64_t NC, int IH, int IW, const 
   const int rc = ufd_fill(p, "vts_upfirdn2d", in, NC, IH, IW, kernel, KH, KW, up, down, px0, px1, py0, py1, out, accumulate);
   if (rc != VTS_OK) return rc;
   p.in = in; p.out = out;
-  if (up == 1 && down == 1 && KH <= UT_MAXK && KW <= UT_MAXK && NC <= 65535)   // Blur: LDS-tiled
+  const bool tiled = up == 1 && down == 1 && KH <= UT_MAXK && KW <= UT_MAXK && NC <= 65535;   // Blur: LDS-tiled
+  if (tiled)
     hipLaunchKernelGGL(ufd_tile_kernel, dim3(cdiv(p.OW, UT_X), cdiv(p.OH, UT_Y), (unsigned)NC), dim3(256), 0, (hipStream_t)stream, p);
   else
     hipLaunchKernelGGL(upfirdn2d_kernel, dim3((unsigned)cdiv64(NC * p.OH * p.OW, 256)), dim3(256), 0, (hipStream_t)stream, p);
   VTS_CHECK_LAUNCH("vts_upfirdn2d");
+  vts_set_kernel(tiled ? "ufd_tile_kernel" : "upfirdn2d_kernel");
   return VTS_OK;
 }
 
@@ -387,10 +389,12 @@ extern "C" int vts_upfirdn2d_bwd(const float* dout, int64_t NC, int IH, int IW, 
       for (int b = 0; b < KW; ++b) q.k[a * KW + b] = p.k[(KH - 1 - a) * KW + (KW - 1 - b)];
     hipLaunchKernelGGL(ufd_tile_kernel, dim3(cdiv(IW, UT_X), cdiv(IH, UT_Y), (unsigned)NC), dim3(256), 0, (hipStream_t)stream, q);
     VTS_CHECK_LAUNCH("vts_upfirdn2d_bwd");
+    vts_set_kernel("ufd_tile_kernel adjoint");
     return VTS_OK;
   }
   hipLaunchKernelGGL(upfirdn2d_adj_kernel, dim3((unsigned)cdiv64(NC * IH * IW, 256)), dim3(256), 0, (hipStream_t)stream, p);
   VTS_CHECK_LAUNCH("vts_upfirdn2d_bwd");
+  vts_set_kernel("upfirdn2d_adj_kernel");
   return VTS_OK;
 }
 
@@ -401,6 +405,7 @@ extern "C" int vts_bias_act(const float* x, const float* bias, const float* res,
   hipLaunchKernelGGL(bias_act_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, (hipStream_t)stream, x, bias, res, total, C, (int)HW, slope,
                      gain, out);
   VTS_CHECK_LAUNCH("vts_bias_act");
+  vts_set_kernel("bias_act_kernel");
   return VTS_OK;
 }
 
@@ -411,6 +416,7 @@ extern "C" int vts_bias_act_bwd(const float* g, const float* x, const float* bia
   hipLaunchKernelGGL(bias_act_bwd_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, (hipStream_t)stream, g, x, bias, total, C, (int)HW,
                      slope, gain, dx);
   VTS_CHECK_LAUNCH("vts_bias_act_bwd");
+  vts_set_kernel("bias_act_bwd_kernel");
   return VTS_OK;
 }
 

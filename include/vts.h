@@ -341,6 +341,43 @@ int vts_w3x3_wino_pack(const float* w, int A, int B, int64_t sa, int64_t sb, int
 int vts_conv3x3_wino_ok(int N, int Cin, int Cout, int H, int W);
 int vts_conv3x3_wino(const float* in, const float* U, const float* bias, float* out, int N, int Cin, int Cout, int H, int W, int out_pad,
                      int ep_mode, const float* ep_add, const float* ep_mask, void* stream);
+/* bf16 path of the frozen VGG stack (csrc/vts_conv3x3_bf16.hip; --lpips_dtype bf16): the LPIPS-VGG16 loss terms on v_mfma_f32_32x32x16_bf16
+ * with fp32 accumulation.  LAYOUT: every activation and gradient map of this path is bf16, CHANNELS LAST, with the next convolution's zero
+ * one-pixel border: [N][H + 2][W + 2][C] (a lane's 8-element k-fragment is one 16-byte load; the LPIPS head reads a pixel's channels
+ * contiguously).  All bf16 pointers must be 16-byte aligned.  fp32 -> bf16 rounds to nearest even.  No float atomics; results are bitwise
+ * repeatable and independent of the batch size and of a sample's index.
+ *   vts_w3x3_bf16_pack   wt[((t * AP/32 + a/32) * BP + b) * 32 + a%32] = bf16(w[a * sa + b * sb + (flip ? 8 - t : t)]), a = the convolution's
+ *                        input channel, b = its output channel, AP = A rounded up to 32, BP = B rounded up to 64, zeros outside A x B;
+ *                        arguments as vts_w3x3_pack (forward: A=Ci,B=Co,sa=9,sb=9Ci,flip=0; input adjoint: A=Co,B=Ci,sa=9Ci,sb=9,flip=1);
+ *                        vts_w3x3_bf16_elems(A, B) bf16 elements
+ *   vts_conv3x3_bf16     conv of in [N][H+2][W+2][Cin] with packed weights; ep_mode
+ *                          1  out [N][H+2][W+2][Cout] bf16 <- max(conv + bias, 0), border zeroed (bias fp32 [Cout], may be NULL; it is read
+ *                             four floats at a time and must be 16-byte aligned too, VTS_ERR_ARG otherwise)
+ *                          2  out (same) <- (conv + ep_add) where ep_mask > 0, else 0, border zeroed; ep_add (optional) / ep_mask: out's layout
+ *                             (the semantics of vts_conv3x3_wide_mask_pad)
+ *                          3  out fp32 DENSE [N][co_store][H][W] <- conv, output channels < co_store only (the first layer's input adjoint:
+ *                             weights packed with B = 3 give Cout = 32, co_store = 3)
+ *                        VTS_ERR_UNSUPPORTED, nothing written, unless vts_conv3x3_bf16_ok: Cin % 32 == 0 and Cout % 32 == 0 (Cin / Cout are
+ *                        the channel counts of in / of the packed weights' padded output; the 3-channel stem runs with its input padded to 32
+ *                        zero-filled channels by vts_bf16_nhwc_pad)
+ *                        Maps of at most 256 pixels whose padded form fits 576 pixels run whole images flattened into one workgroup's
+ *                        256 MFMA columns (instance conv3x3_bf16_kernel<ep, flat>: the 4 x 4 / 2 x 2 maps of the deep layers on patch stacks); the
+ *                        result of a pixel is the same accumulation chain in either instance
+ *   vts_bf16_nhwc_pad    x fp32 [N][C][H][W] -> out [N][H+2][W+2][CP], zero border, zero channels >= C (CP % 8 == 0)
+ *   vts_maxpool2_bf16    out [N][H/2+2][W/2+2][C] <- MaxPool2d(2, 2) of z [N][H+2][W+2][C] (ReLU outputs), zero border; exact
+ *   vts_maxpool2_bf16_bwd  gz [N][H+2][W+2][C] <- g [N][H/2+2][W/2+2][C] routed by the rule of vts_maxpool2_relu_bwd (+ g2, z's layout, where z > 0)
+ *   vts_lpips_layer_bf16 vts_lpips_layer on two such feature maps: arithmetic in fp32, dz0 (optional; z0's layout, border zeroed) in bf16;
+ *                        C in {64, 128, 256, 512} */
+int64_t vts_w3x3_bf16_elems(int A, int B);
+int vts_w3x3_bf16_pack(const float* w, int A, int B, int64_t sa, int64_t sb, int flip, void* wt, void* stream);
+int vts_conv3x3_bf16_ok(int N, int Cin, int Cout, int H, int W);
+int vts_conv3x3_bf16(const void* in, const void* wt, const float* bias, void* out, int N, int Cin, int Cout, int H, int W, int ep_mode,
+                     const void* ep_add, const void* ep_mask, int co_store, void* stream);
+int vts_bf16_nhwc_pad(const float* x, int N, int C, int H, int W, int CP, void* out, void* stream);
+int vts_maxpool2_bf16(const void* z, int N, int C, int H, int W, void* out, void* stream);
+int vts_maxpool2_bf16_bwd(const void* g, const void* z, const void* g2, int N, int C, int H, int W, void* gz, void* stream);
+int vts_lpips_layer_bf16(const void* z0, const void* z1, int N, int C, int H, int W, const float* w, float coeff, int64_t* loss_slot,
+                         void* dz0, float grad_coeff, void* stream);
 int64_t vts_conv3x3_wide_ws_floats(int N, int Cin, int Cout, int H, int W);
 int vts_conv3x3s2_wide(const float* in, const float* wt, const float* bias, float* out, int N, int Cin, int Cout, int OH, int OW,
                        float* ws, int64_t ws_floats, void* stream);

@@ -89,6 +89,9 @@ class SinSKITGModel(BaseModel):
         # separated); the reference gets them from `lpips.LPIPS(net="vgg")`, which downloads (sinskitG_model.py:495).  Without a file the
         # perceptual terms run on seeded stand-in weights and `loss_lpips_pretrained` / `metric_lpips_pretrained` say so.
         parser.add_argument("--lpips_weights", type=str, default="")
+        # not a reference flag: number format of the frozen VGG16 inside the two LPIPS LOSS terms (lambda_G1_lpips, lambda_G2_lpips).  bf16: the
+        # stack on the bf16 matrix cores with fp32 accumulation (csrc/vts_conv3x3_bf16.hip); the metrics (I_LPIPS / T_LPIPS) stay fp32
+        parser.add_argument("--lpips_dtype", type=str, default="fp32", choices=("fp32", "bf16"))
         # ... and of the AlexNet variant the reference evaluates with in the test phase (lpips.LPIPS(net="alex"), sinskitG_model.py:501:
         # torchvision alexnet features + lpips v0.1 lin layers)
         parser.add_argument("--lpips_alex_weights", type=str, default="")
@@ -232,6 +235,7 @@ class SinSKITGModel(BaseModel):
                 self.optimizers.append(self.optimizer_D2)
         # LPIPS-VGG16 (criterionLPIPS_vgg, sinskitG_model.py:495): frozen, not a saved network
         self.netLPIPS = None
+        self.loss_lpips_dtype = getattr(opt, "lpips_dtype", "fp32")       # the loss terms only; the I_LPIPS / T_LPIPS metrics run fp32
         if self.isTrain and (opt.lambda_G1_lpips > 0 or opt.lambda_G2_lpips > 0):
             self._lpips_net()
         self._loss_buf = ops.loss_slots(len(LOSS_SLOTS), self.device)     # int64 fixed point (order-independent accumulation)
@@ -1014,7 +1018,7 @@ class SinSKITGModel(BaseModel):
             # criterionLPIPS_vgg(fake_I, real_I).mean() * lambda (:1711)
             from vts import perceptual as P_
             P_.lpips_term(self.netLPIPS, self.fake_I, self.real_I, opt.lambda_G1_lpips / n, slot["G_lpips"], grad_into=self._d_fake_I,
-                          grad_accumulate=self._have_dI)
+                          grad_accumulate=self._have_dI, dtype=self.loss_lpips_dtype)
             self._have_dI = True
         d_fake_T = None
         d_patch = None
@@ -1034,7 +1038,7 @@ class SinSKITGModel(BaseModel):
             #  (all three tensors are whole contiguous buffers: fake_T_concat, the patch set's real_T, d_patch; view() refuses anything else)
             f, r = self.fake_T_concat, ts["real_T"]
             P_.lpips_term(self.netLPIPS, f.view(2 * P, 1, 32, 32), r.view(2 * P, 1, 32, 32), opt.lambda_G2_lpips / n, slot["G2_lpips"],
-                          grad_into=d_patch.view(2 * P, 1, 32, 32), grad_accumulate=have)
+                          grad_into=d_patch.view(2 * P, 1, 32, 32), grad_accumulate=have, dtype=self.loss_lpips_dtype)
         if d_patch is not None:
             d_fake_T = torch.empty(n, 2, h, w, device=dev)
             ops.patch_scatter_bwd(d_patch, 0, 2, ts["offx"], ts["offy"], nt, 32, d_fake_T)

@@ -168,6 +168,8 @@ SYMBOLS = [
     "vts_gemm_f16_aux", "vts_layernorm_rows_bwd", "vts_vit_attention_bwd", "vts_clip_visual_tape_floats", "vts_clip_visual_forward_tape",
     "vts_clip_visual_weight_t_halfs", "vts_clip_visual_backward_ws_floats", "vts_clip_visual_backward", "vts_clip_area_preprocess",
     "vts_clip_area_preprocess_bwd",
+    "vts_w3x3_bf16_elems", "vts_w3x3_bf16_pack", "vts_conv3x3_bf16_ok", "vts_conv3x3_bf16", "vts_bf16_nhwc_pad", "vts_maxpool2_bf16", "vts_maxpool2_bf16_bwd",
+    "vts_lpips_layer_bf16",
 ]
 
 
@@ -207,6 +209,8 @@ def load():
     lib.vts_w3x3_wino_floats.argtypes = [C.c_int, C.c_int]
     lib.vts_w3x3_wino_floats.restype = C.c_int64
     lib.vts_unet_forward_ws_floats.restype = C.c_int64
+    lib.vts_w3x3_bf16_elems.argtypes = [C.c_int, C.c_int]
+    lib.vts_w3x3_bf16_elems.restype = C.c_int64
     lib.vts_unet_backward_ws_floats.argtypes = [C.POINTER(UnetDesc)]
     lib.vts_unet_backward_ws_floats.restype = C.c_int64
     lib.vts_patchgan_backward_ws_floats.argtypes = [C.POINTER(PatchganDesc)]
@@ -368,6 +372,11 @@ def load():
         "vts_clip_visual_backward": [C.POINTER(ClipVisualCfg), vp, vp, vp, i64, i, vp, C.POINTER(C.c_int), i, vp, vp, vp, i64, vp],
         "vts_clip_area_preprocess": [vp, i, i, i, i, vp, i, vp],
         "vts_clip_area_preprocess_bwd": [vp, i, i, i, i, vp, vp],
+        "vts_w3x3_bf16_pack": [vp, i, i, i64, i64, i, vp, vp], "vts_conv3x3_bf16_ok": [i, i, i, i, i],
+        "vts_conv3x3_bf16": [vp, vp, vp, vp, i, i, i, i, i, i, vp, vp, i, vp],
+        "vts_bf16_nhwc_pad": [vp, i, i, i, i, i, vp, vp], "vts_maxpool2_bf16": [vp, i, i, i, i, vp, vp],
+        "vts_maxpool2_bf16_bwd": [vp, vp, vp, i, i, i, i, vp, vp],
+        "vts_lpips_layer_bf16": [vp, vp, i, i, i, i, vp, f, vp, vp, f, vp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)

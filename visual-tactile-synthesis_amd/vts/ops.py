@@ -1586,6 +1586,103 @@ def lpips_input_bwd(g, scale, dx, cx, accumulate=False, nstride=None):
     return dx
 
 
+# ---- bf16 path of the frozen VGG stack (include/vts.h): bf16, channels last, [N, H + 2, W + 2, C] with a zero one-pixel border ----
+EP_BF16_RELU_PAD, EP_BF16_MASK_PAD, EP_BF16_DX = 1, 2, 3
+
+
+def w3x3_bf16_pack(w, mode, tag=None):
+    """bf16 packing (round to nearest even) of a 3x3 nn.Conv2d weight [Co,Ci,3,3] for conv3x3_bf16 in a persistent buffer;
+    mode conv_fwd | conv_adj (taps flipped, channels swapped)"""
+    d0, d1 = w.shape[0], w.shape[1]
+    A, B, sa, sb, flip = {"conv_fwd": (d1, d0, 9, 9 * d1, 0), "conv_adj": (d0, d1, 9 * d1, 9, 1)}[mode]
+    lib = L.load()
+    key = ("bf16", w.data_ptr(), tuple(w.shape), mode, tag)
+    buf = _staging.get(key)
+    if buf is None:
+        buf = _staging[key] = torch.empty(int(lib.vts_w3x3_bf16_elems(A, B)), dtype=torch.bfloat16, device=w.device)
+    _run("w3x3_bf16_pack", 4.0 * w.numel() + 2.0 * buf.numel(), 0.0, lib.vts_w3x3_bf16_pack, w.data_ptr(), A, B, sa, sb, flip, buf.data_ptr(), L.stream())
+    return buf
+
+
+def conv3x3_bf16_ok(n, ci, co, h, w):
+    return bool(L.load().vts_conv3x3_bf16_ok(n, ci, co, h, w))
+
+
+def conv3x3_bf16(p, wt, bias, out, ep_mode, add=None, mask=None):
+    """3x3 convolution of p [N, H + 2, W + 2, Ci] (bf16) on the bf16 MFMAs.  ep_mode EP_BF16_RELU_PAD: out [N, H + 2, W + 2, Co] bf16 <-
+    max(conv + bias, 0); EP_BF16_MASK_PAD: out <- (conv + add) where mask > 0 (add / mask: out's layout); EP_BF16_DX: out fp32 dense
+    [N, co, H, W] (the weights' output channels padded to a multiple of 32).  Raises where vts_conv3x3_bf16_ok declines."""
+    n, ph, pw, ci = p.shape
+    h, w = ph - 2, pw - 2
+    assert p.dtype == torch.bfloat16 and wt.dtype == torch.bfloat16 and p.is_contiguous() and out.is_contiguous()
+    if ep_mode == EP_BF16_DX:
+        co_store = out.shape[1]
+        co = (co_store + 31) // 32 * 32
+        assert out.dtype == torch.float32 and out.shape == (n, co_store, h, w)
+    else:
+        co_store = co = out.shape[3]
+        assert out.dtype == torch.bfloat16 and out.shape == (n, ph, pw, co)
+        for t in (add, mask):
+            assert t is None or (t.shape == out.shape and t.dtype == torch.bfloat16 and t.is_contiguous())
+    assert wt.numel() == L.load().vts_w3x3_bf16_elems(ci, co)
+    if TIMER is not None:
+        global DETAIL
+        DETAIL = "N%d %dx%dx%d -> %dx%dx%d bf16 %s" % (n, ci, h, w, co, h, w, ("", "relu+pad", "mask+pad", "dx")[ep_mode])
+    _run("conv3x3_bf16", 2.0 * (p.numel() + wt.numel() + out.numel() * (1 + (add is not None) + (mask is not None))), 2.0 * n * h * w * co * ci * 9,
+         L.load().vts_conv3x3_bf16, p.data_ptr(), wt.data_ptr(), L.ptr(bias), out.data_ptr(), n, ci, co, h, w, ep_mode, L.ptr(add), L.ptr(mask),
+         co_store, L.stream())
+    return out
+
+
+def bf16_nhwc_pad(x, cp=32):
+    """fp32 [N, C, H, W] -> bf16 [N, H + 2, W + 2, cp]: zero border, zero channels >= C (the stem's operand of the bf16 path)"""
+    n, c, h, w = x.shape
+    assert x.dtype == torch.float32 and x.is_contiguous()
+    out = torch.empty(n, h + 2, w + 2, cp, dtype=torch.bfloat16, device=x.device)
+    if TIMER is not None:
+        global DETAIL
+        DETAIL = "N%d %dx%dx%d -> %d channels bf16" % (n, c, h, w, cp)
+    _run("bf16_nhwc_pad", 4.0 * x.numel() + 2.0 * out.numel(), 0.0, L.load().vts_bf16_nhwc_pad, x.data_ptr(), n, c, h, w, cp, out.data_ptr(), L.stream())
+    return out
+
+
+def maxpool2_bf16(z):
+    n, ph, pw, c = z.shape
+    assert z.dtype == torch.bfloat16 and z.is_contiguous()
+    out = torch.empty(n, (ph - 2) // 2 + 2, (pw - 2) // 2 + 2, c, dtype=torch.bfloat16, device=z.device)
+    if TIMER is not None:
+        global DETAIL
+        DETAIL = "N%d %dx%dx%d bf16" % (n, c, ph - 2, pw - 2)
+    _run("maxpool2_bf16", 2.0 * (z.numel() + out.numel()), 0.0, L.load().vts_maxpool2_bf16, z.data_ptr(), n, c, ph - 2, pw - 2, out.data_ptr(), L.stream())
+    return out
+
+
+def maxpool2_bf16_bwd(g, z, g2=None):
+    """g: gradient w.r.t. the pooled map, [N, H/2 + 2, W/2 + 2, C]; z (and the tap gradient g2): [N, H + 2, W + 2, C]"""
+    n, ph, pw, c = z.shape
+    assert g.shape == (n, (ph - 2) // 2 + 2, (pw - 2) // 2 + 2, c) and all(t is None or (t.dtype == torch.bfloat16 and t.is_contiguous()) for t in (g, z, g2))
+    assert g2 is None or g2.shape == z.shape
+    gz = torch.empty_like(z)
+    if TIMER is not None:
+        global DETAIL
+        DETAIL = "N%d %dx%dx%d bf16%s" % (n, c, ph - 2, pw - 2, " + tap gradient" if g2 is not None else "")
+    _run("maxpool2_bf16_bwd", 2.0 * ((2 + (g2 is not None)) * z.numel() + g.numel()), 0.0, L.load().vts_maxpool2_bf16_bwd, g.data_ptr(), z.data_ptr(), L.ptr(g2),
+         n, c, ph - 2, pw - 2, gz.data_ptr(), L.stream())
+    return gz
+
+
+def lpips_layer_bf16(z0, z1, w, coeff, loss_slot, dz0=None, grad_coeff=0.0):
+    """lpips_layer on bf16 channels-last features [N, H + 2, W + 2, C]; dz0 (z0's layout, bf16) gets its zero border from the kernel"""
+    n, ph, pw, c = z0.shape
+    assert z1.shape == z0.shape and z0.dtype == z1.dtype == torch.bfloat16 and z0.is_contiguous() and z1.is_contiguous() and w.numel() == c
+    assert dz0 is None or (dz0.shape == z0.shape and dz0.dtype == torch.bfloat16 and dz0.is_contiguous())
+    if TIMER is not None:
+        global DETAIL
+        DETAIL = "N%d %dx%dx%d bf16%s" % (n, c, ph - 2, pw - 2, " + dz0" if dz0 is not None else "")
+    _run("lpips_layer_bf16", 2.0 * z0.numel() * (2 + (dz0 is not None)), 6.0 * z0.numel(), L.load().vts_lpips_layer_bf16, z0.data_ptr(), z1.data_ptr(), n, c,
+         ph - 2, pw - 2, w.data_ptr(), coeff, L.ptr(loss_slot), L.ptr(dz0), grad_coeff, L.stream())
+
+
 def _chw_dense(t):
     """the channels of every sample lie densely behind each other (a channel view of a contiguous NCHW tensor does; its batch stride is free)"""
     _, c, h, w = t.shape

@@ -13,6 +13,11 @@ z, relu applied by the reader, padding as one fused pass (pad_affine with ReLU /
 GEMM-class MFMA kernels (ops.conv3x3_wide; the 3 -> 64 stem as one 8-channel chunk) with weights packed ONCE (the stacks are frozen).
 The backward is the input adjoint only (no weight gradients): the same GEMM kernel on flipped / transposed packing,
 vts_maxpool2_relu_bwd behind a block, and the stem's 64 -> 3 adjoint as 4x4 tap blocks on the generator's kernel (ops.convk_bwd_data).
+
+lpips_term(dtype="bf16") (--lpips_dtype bf16: the two LPIPS LOSS terms of the training step; the metrics stay fp32) runs the same schedule on
+the bf16 matrix cores (csrc/vts_conv3x3_bf16.hip): every activation and gradient map bf16, channels last, zero-bordered [N, H + 2, W + 2, C];
+fp32 accumulation, fp32 bias, fp32 LPIPS arithmetic.  The stem sees its 3 input channels padded to 32 zero-filled ones and its adjoint writes
+the dense fp32 gradient.  A layer the bf16 kernel declines raises: the frozen stack never mixes precisions silently.
 """
 import os
 from . import tune
@@ -163,6 +168,103 @@ def vgg_backward(net, zs, tap_grads, x_shape, masked_taps=False):
     return dx
 
 
+def _bf16w(net, k, mode):
+    """bf16-packed weights of convolution k (frozen stack: packed once)"""
+    key = (k, mode, "bf16")
+    buf = net._packed.get(key)
+    if buf is None:
+        buf = net._packed[key] = ops.w3x3_bf16_pack(net.convs[k].weight, mode, tag="frozen%d" % id(net))
+    return buf
+
+
+def _bf16_must(n, ci, co, h, w, k):
+    if not ops.conv3x3_bf16_ok(n, ci, co, h, w):
+        raise RuntimeError("lpips_dtype bf16: convolution %d (N%d, %d -> %d channels on %d x %d) is not taken by vts_conv3x3_bf16; "
+                           "the frozen stack does not mix precisions" % (k, n, ci, co, h, w))
+
+
+def vgg_forward_bf16(net, x, keep_all=True):
+    """x fp32 [N, 3, H, W] in the network's input space.  Returns (zs, pools): zs {conv index: relu(z) as bf16 [N, H + 2, W + 2, C]} (every
+    convolution when keep_all, else the taps), pools {conv index: its pooled operand} (keep_all: the backward masks with it)."""
+    n = x.shape[0]
+    zs, pools = {}, {}
+    prev = ops.bf16_nhwc_pad(x, 32)
+    last = max(net.taps)
+    for k, pooled in _layout(net):
+        if k > last:
+            break
+        conv = net.convs[k]
+        co = conv.weight.shape[0]
+        if pooled:
+            prev = ops.maxpool2_bf16(prev)
+            if keep_all:
+                pools[k] = prev
+        hh, ww, ci = prev.shape[1] - 2, prev.shape[2] - 2, prev.shape[3]
+        _bf16_must(n, ci, co, hh, ww, k)
+        out = torch.empty(n, hh + 2, ww + 2, co, dtype=torch.bfloat16, device=x.device)
+        ops.conv3x3_bf16(prev, _bf16w(net, k, "conv_fwd"), conv.bias, out, ops.EP_BF16_RELU_PAD)
+        if keep_all or k in net.taps:
+            zs[k] = out
+        prev = out
+    return zs, pools
+
+
+def vgg_backward_bf16(net, zs, pools, tap_grads, x_shape):
+    """fp32 gradient w.r.t. the network input from {tap conv index: masked gradient w.r.t. relu(z_tap)} (ops.lpips_layer_bf16 writes them so);
+    zs / pools from vgg_forward_bf16(keep_all=True).  An input adjoint carries the ReLU mask (and tap gradient) of the layer in front in its
+    epilogue; in front of a pooling the mask is the pooled map (a window whose maximum is 0 routes nothing) and ops.maxpool2_bf16_bwd follows."""
+    lay = [e for e in _layout(net) if e[0] <= max(net.taps)]
+    n = x_shape[0]
+    top = max(k for k in tap_grads)
+    G = None
+    for idx in range(len(lay) - 1, 0, -1):
+        k, pooled = lay[idx]
+        if k > top:
+            continue
+        if k == top:
+            G = tap_grads[k]
+        co, ci = net.convs[k].weight.shape[:2]
+        kf = lay[idx - 1][0]
+        ft, T = zs[kf], tap_grads.get(kf)
+        _bf16_must(n, co, ci, G.shape[1] - 2, G.shape[2] - 2, k)
+        if pooled:
+            out = torch.empty_like(pools[k])
+            ops.conv3x3_bf16(G, _bf16w(net, k, "conv_adj"), None, out, ops.EP_BF16_MASK_PAD, mask=pools[k])
+            G = ops.maxpool2_bf16_bwd(out, ft, g2=T)
+        else:
+            out = torch.empty_like(ft)
+            ops.conv3x3_bf16(G, _bf16w(net, k, "conv_adj"), None, out, ops.EP_BF16_MASK_PAD, add=T, mask=ft)
+            G = out
+    if G is None:
+        raise RuntimeError("vgg_backward_bf16: no tap gradient given")
+    dx = torch.empty(x_shape, dtype=torch.float32, device=G.device)
+    _bf16_must(n, G.shape[3], 32, x_shape[2], x_shape[3], 0)
+    ops.conv3x3_bf16(G, _bf16w(net, 0, "conv_adj"), None, dx, ops.EP_BF16_DX)
+    return dx
+
+
+def _lpips_term_bf16(net, fake, real, coeff, loss_slot, grad_into, grad_accumulate, cx, nstride_fake, nstride_real, grad_nstride):
+    want = grad_into is not None
+    n = fake.shape[0]
+    y = torch.empty(2 * n, 3, fake.shape[2], fake.shape[3], dtype=torch.float32, device=fake.device)     # rows [0, N) fake, [N, 2 N) real
+    ops.lpips_input(fake, net.shift, net.scale, nstride=nstride_fake, channels=cx, out=y[:n])
+    ops.lpips_input(real, net.shift, net.scale, nstride=nstride_real, channels=cx, out=y[n:])
+    zz, pools = vgg_forward_bf16(net, y, keep_all=want)
+    x_shape = (n,) + tuple(y.shape[1:])
+    del y
+    tap_grads = {}
+    for i, k in enumerate(net.taps):
+        t = zz[k]
+        dz = torch.empty_like(t[:n]) if want else None
+        ops.lpips_layer_bf16(t[:n], t[n:], net.lins[i].view(-1), coeff, loss_slot, dz0=dz, grad_coeff=coeff)
+        if want:
+            tap_grads[k] = dz
+    if not want:
+        return None
+    gy = vgg_backward_bf16(net, {k: t[:n] for k, t in zz.items()}, {k: t[:n] for k, t in pools.items()}, tap_grads, x_shape)
+    return ops.lpips_input_bwd(gy, net.scale, grad_into, cx, accumulate=grad_accumulate, nstride=grad_nstride)
+
+
 def alex_forward(net, x):
     """AlexNet feature stack of models/perceptual.py:LpipsAlex on the HIP kernels; x [N, 3, H, W] in the network's input space.
     Returns {k: raw output z of convolution k} (the taps read relu(z) on load, like the VGG taps).
@@ -206,11 +308,16 @@ def lpips_alex_value(net, a, b, coeff, loss_slot, channels=None):
 
 
 def lpips_term(net, fake, real, coeff, loss_slot, grad_into=None, grad_accumulate=False, channels=None, nstride_fake=None, nstride_real=None,
-               grad_nstride=None):
+               grad_nstride=None, dtype="fp32"):
     """loss_slot += coeff * sum_n LPIPS(fake_n, real_n); grad_into (+)= coeff * d(.)/d fake when given.
+    dtype "bf16": the frozen stack on the bf16 matrix cores (the training step's loss terms under --lpips_dtype bf16); "fp32": as ever.
     fake / real: [N, 3, H, W], or 1-channel VIEWS (channels=1, nstride_* = batch stride of the tensor they are a channel of):
     the ScalingLayer broadcasts the single channel to three, as lpips does for the tactile gx / gy images."""
     cx = fake.shape[1] if channels is None else channels
+    if dtype not in ("fp32", "bf16"):
+        raise ValueError("lpips_term: dtype %r (fp32 | bf16)" % (dtype,))
+    if dtype == "bf16":
+        return _lpips_term_bf16(net, fake, real, coeff, loss_slot, grad_into, grad_accumulate, cx, nstride_fake, nstride_real, grad_nstride)
     want = grad_into is not None
     n = fake.shape[0]
     if want:

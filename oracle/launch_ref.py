@@ -1,6 +1,7 @@
 """Float64 judge of the C ABI's conv / weight-gradient / normalisation semantics, of the step's glue kernels (loss, optimiser,
 pyramid, patches, post-processing, augmentation, staging, sampler) and of the padding / resampling / FIR operators (pad, blur, weight taps,
-table resampling, upfirdn2d, bias_act, nearest, tanh_bwd; their units are derived rounding counts, see that section), written from the
+table resampling, upfirdn2d, bias_act, nearest, tanh_bwd; their units are derived rounding counts, see that section) and of the fp32 glue of
+the perceptual terms (pooling, masks, the LPIPS head, the ReLU-L1, input scaling and stacking: the last section), written from the
 formulas in include/vts.h (not from the kernels).  Checker only: the product never imports it.
 
 Every function returns {name: (ref, unit)} with float64 tensors: `ref` the exact value, `unit` the elementwise error scale of an
@@ -1213,3 +1214,200 @@ def tanh_bwd(g, y):
     """vts_tanh_bwd: dz = g (1 - y^2): the square, the subtraction, the product: 3 roundings of |g| (1 + y^2)"""
     g, y = _f64(g), _f64(y)
     return {"dz": (g * (1 - y * y), 3 * U * g.abs() * (1 + y * y))}
+
+
+# ---- the fp32 glue of the perceptual terms (csrc/vts_perceptual.hip, vts_zero_border) ---------------------------------------------------------
+# Written from the formulas of include/vts.h.  Operands are passed DENSE (the interior of a zpad-padded tensor; the test lays them out).
+# Data movement, masks and single maxima are bitwise (unit None, the reference already in its final fp32 value, +0.0 for every zero).  The
+# arithmetic outputs carry the derived unit of the section above, (r + K) u absref.  Loss slots are judged as (slot - start) / 2^40 against
+# the any-order bound of a K-term fp32 sum, (K - 1) u sum |terms|, plus the per-term roundings and 2^-41 for each workgroup's rounding to
+# fixed point; rows whose addends sum exactly in fp32 (operands on a dyadic grid) carry the fixed-point rounding alone.
+
+def _zpad(t, pad):
+    return torch.nn.functional.pad(t, (pad, pad, pad, pad)) + 0.0
+
+
+def maxpool2_relu_pad(z, pad):
+    """vts_maxpool2_relu_pad: out [NC, H/2 + 2 pad, W/2 + 2 pad] = zero-padded MaxPool2d(2, 2)(relu(z)), z [NC, H, W]; an odd last row /
+    column belongs to no window.  A maximum of four inputs and 0: bitwise."""
+    z = _f64(z)
+    return {"out": (_zpad(torch.nn.functional.max_pool2d(z.clamp_min(0.0).unsqueeze(0), 2, 2)[0], pad), None)}
+
+
+def maxpool3s2_relu_pad(z, pad):
+    """vts_maxpool3s2_relu_pad: the 3 x 3 window at (2 y, 2 x) of relu(z), OH = (H - 3) / 2 + 1, zero border of `pad`: bitwise"""
+    z = _f64(z)
+    return {"out": (_zpad(torch.nn.functional.max_pool2d(z.clamp_min(0.0).unsqueeze(0), 3, 2)[0], pad), None)}
+
+
+def s2d4_pad(x, pad, oh, ow):
+    """vts_s2d4_pad: out[n, (c * 4 + i) * 4 + j, Y, X] = xp[n, c, 4 Y + i, 4 X + j], xp = x zero-padded by `pad` and zero beyond: bitwise"""
+    x = _f64(x)
+    n, c, h, w = x.shape
+    xp = x.new_zeros(n, c, 4 * oh, 4 * ow)
+    hh, ww = max(min(h, 4 * oh - pad), 0), max(min(w, 4 * ow - pad), 0)
+    xp[:, :, pad:pad + hh, pad:pad + ww] = x[:, :, :hh, :ww]
+    return {"out": (xp.view(n, c, oh, 4, ow, 4).permute(0, 1, 3, 5, 2, 4).reshape(n, 16 * c, oh, ow) + 0.0, None)}
+
+
+def vgg_stack_input(fake_I, real_I, fake_T, real_T):
+    """vts_vgg_stack_input: out [6 N, 3, H + 2, W + 2], zero border, row groups fake_I, fake_gx x 3, fake_gy x 3, real_I, real_gx x 3,
+    real_gy x 3 (gx, gy = channels 0, 1 of the tactile tensors): bitwise"""
+    rows = []
+    for img, tac in ((fake_I, fake_T), (real_I, real_T)):
+        img, tac = _f64(img), _f64(tac)
+        rows += [img[:, :3], tac[:, 0:1].expand(-1, 3, -1, -1), tac[:, 1:2].expand(-1, 3, -1, -1)]
+    return {"out": (_zpad(torch.cat(rows, 0), 1), None)}
+
+
+def zero_border(buf, pad):
+    """vts_zero_border: buf [NC, H + 2 pad, W + 2 pad], the border of `pad` pixels <- 0.  Returns the whole buffer after the call and
+    "own", the mask [H + 2 pad, W + 2 pad] of the border (the interior is not the call's: it comes back bitwise)."""
+    ref = _f64(buf).clone()
+    own = torch.ones(ref.shape[-2:], dtype=torch.bool)
+    own[pad:-pad, pad:-pad] = False
+    ref[..., own] = 0.0
+    return {"buf": (ref, None), "own": own}
+
+
+def relu_mask_pad(g, g2, z, pad):
+    """vts_relu_mask_pad: out = zero-padded (g + g2) where z > 0, else 0; g or g2 may be None.  One fp32 add: exact for operands on a
+    common dyadic grid (the test's), then the float64 value is the fp32 result: bitwise"""
+    z = _f64(z)
+    t = torch.zeros_like(z)
+    for a in (g, g2):
+        if a is not None:
+            t = t + _f64(a)
+    return {"out": (_zpad(torch.where(z > 0, t, torch.zeros_like(t)), pad), None)}
+
+
+def maxpool2_relu_bwd(g, z, g2, pad):
+    """vts_maxpool2_relu_bwd: gz [NC, H + 2 pad, W + 2 pad] = zero-padded (g [NC, H/2, W/2] routed to the FIRST element, in row-major order
+    of the 2 x 2 window, that holds the window's maximum -- only where that maximum is positive -- plus g2 where z > 0).  Elements of an
+    odd last row / column get the tap alone.  One add of two operands on a dyadic grid: bitwise."""
+    g, z = _f64(g), _f64(z)
+    nc, h, w = z.shape
+    oh, ow = h // 2, w // 2
+    e = z[:, :2 * oh, :2 * ow].reshape(nc, oh, 2, ow, 2).permute(0, 1, 3, 2, 4).reshape(nc, oh, ow, 4)
+    m = e.max(-1).values
+    first = torch.full(m.shape, 3, dtype=torch.int64)
+    for k in (2, 1, 0):
+        first = torch.where(e[..., k] == m, torch.full_like(first, k), first)
+    route = torch.zeros_like(e)
+    route.scatter_(-1, first.unsqueeze(-1), torch.where(m > 0, g, torch.zeros_like(g)).unsqueeze(-1))
+    out = torch.zeros_like(z)
+    out[:, :2 * oh, :2 * ow] = route.reshape(nc, oh, ow, 2, 2).permute(0, 1, 3, 2, 4).reshape(nc, 2 * oh, 2 * ow)
+    if g2 is not None:
+        out = out + torch.where(z > 0, _f64(g2), torch.zeros_like(z))
+    return {"gz": (_zpad(out, pad), None)}
+
+
+def l1_relu(za, zb, coeff, workgroups, exact_sum=False):
+    """vts_l1_relu: "loss" = coeff * sum |relu(za) - relu(zb)|, "grad" = coeff * sign(.) (bitwise: +-coeff or 0).  The loss: one rounding
+    per term (the subtraction; relu and |.| are exact) and K = n addends in any order: K u coeff sum |d| + workgroups 2^-41.  exact_sum
+    (operands on a 2^-6 grid: every partial sum is exact in fp32): the fixed-point rounding alone."""
+    coeff = _f32(coeff)
+    d = _f64(za).reshape(-1).clamp_min(0.0) - _f64(zb).reshape(-1).clamp_min(0.0)
+    unit = workgroups * 2.0 ** -41 + (0.0 if exact_sum else U * d.numel() * abs(coeff) * d.abs().sum())
+    return {"loss": ((coeff * d.abs().sum()).reshape(1), torch.as_tensor(unit, dtype=torch.float64).reshape(1)),
+            "grad": (coeff * torch.sign(d) + 0.0, None)}
+
+
+def lpips_input(x, shift3, scale3):
+    """vts_lpips_input: y [N, 3, HW] = (x - shift_c) / scale_c, x [N, 1 | 3, HW] (one channel: broadcast).  Three roundings: the host's
+    fp32 reciprocal 1 / scale, the host's quotient -shift / scale, the fmaf: unit = 3 u (|x| + |shift|) / |scale|"""
+    x = _f64(x)
+    sh = torch.tensor([_f32(v) for v in shift3], dtype=torch.float64).view(1, 3, 1)
+    sc = torch.tensor([_f32(v) for v in scale3], dtype=torch.float64).view(1, 3, 1)
+    x = x.expand(-1, 3, -1)
+    return {"y": ((x - sh) / sc, 3 * U * (x.abs() + sh.abs()) / sc.abs())}
+
+
+def lpips_input_bwd(g, scale3, cx, dx0=None):
+    """vts_lpips_input_bwd: dx [N, Cx, HW] (+)= g_c / scale_c (Cx = 3), sum_c g_c / scale_c (Cx = 1), g [N, 3, HW].  Roundings: the host's
+    fp32 reciprocal and the product on every term (2: the reciprocal counts here as it does in vts_lpips_input), two adds for the sum of
+    three (4), one more with accumulate."""
+    g = _f64(g)
+    sc = torch.tensor([_f32(v) for v in scale3], dtype=torch.float64).view(1, 3, 1)
+    ref, a, r = g / sc, g.abs() / sc.abs(), 2
+    if cx == 1:
+        ref, a, r = ref.sum(1, keepdim=True), a.sum(1, keepdim=True), 4
+    if dx0 is not None:
+        o = _f64(dx0)
+        ref, a, r = ref + o, a + o.abs(), r + 1
+    return {"dx": (ref, r * U * a)}
+
+
+def vgg_stack_input_bwd(dx, n, dI0=None, dT0=None):
+    """vts_vgg_stack_input_bwd: dx [3 N, 3, HW] -> "dI" [N, 3, HW] (+)= dx[0:N] (a copy: unit 0; one rounding with accumulate),
+    "dT" [N, 2, HW] (+)= (dx[(1 + c) N + n, 0] + dx[.., 1]) + dx[.., 2] (two roundings; three with accumulate)"""
+    dx = _f64(dx)
+    dI, aI, rI = dx[:n], dx[:n].abs(), 0
+    t = torch.stack([dx[n:2 * n], dx[2 * n:3 * n]], 1)              # [N, 2, 3, HW]
+    dT, aT, rT = t.sum(2), t.abs().sum(2), 2
+    if dI0 is not None:
+        oI, oT = _f64(dI0), _f64(dT0)
+        dI, aI, rI, dT, aT, rT = dI + oI, aI + oI.abs(), 1, dT + oT, aT + oT.abs(), 3
+    return {"dI": (dI, rI * U * aI), "dT": (dT, rT * U * aT)}
+
+
+def lpips_layer_judge(f0, f1, w, coeff, grad_coeff, workgroups=None, raw=False, addends=None):
+    """f0, f1 [N, C, H, W] >= 0 (float64), w [C].  Returns value (float64 scalar: what the call adds to the slot), its bound,
+    dz0 [N, C, H, W] and its fp32 bound (vts_lpips_layer_bf16: bf16-exact operands, and the bf16 store adds 2^-8 |dz0|).
+    workgroups: of the fixed-point term (None: the bf16 head's, one per 32 pixels of the padded map); raw: f0 / f1 are raw convolution
+    outputs z (vts_lpips_layer with zpad = 0): ReLU on load, gradient exactly 0 where z0 <= 0; addends: the number K of pixel terms the
+    slot value sums, for the any-order bound (K - 1) u (None: the bf16 head's 26, below).
+
+    The unit is a derived linear rounding count ((r + K) u absref): nothing in it is measured.
+      s = sum_c f^2 (C positive terms, any order)          relative error <= C u
+      r = sqrt(s), r + eps, i = 1 / (r + eps)               rho = C / 2 + 3 roundings on i (sqrt, add, divide: one each, correctly rounded)
+      t_c = f0_c i0 - f1_c i1                               |dt_c| <= (rho + 2) u A_c, A_c = f0_c i0 + f1_c i1 (two products, one subtraction)
+      d = sum_c w_c t_c^2                                   |dd| <= u sum_c w_c (2 (rho + 2) A_c |t_c| + (2 + C) t_c^2)
+      value = coeff / HW sum_pixels d                       + 26 u per term for the thread / wave / workgroup sums (<= 16 + 6 + 4 additions on any term's path)
+                                                            + 2^-41 per workgroup (its rounding to the fixed-point slot)
+      S = sum_c w_c t_c f0_c                                E_S = u sum_c w_c f0_c ((rho + 2) A_c + (2 + C) |t_c|)
+      k1 = 2 g / HW i0                                      rho + 3 roundings
+      k2 = 2 g / HW S i0^2 / r0                             |dk2| <= |2 g / HW| i0^2 / r0 (E_S + |S| u (2 rho + C / 2 + 6))
+      dz0_c = k1 w_c t_c - k2 f0_c where f0_c > 0           u |k1| w_c ((rho + 5) |t_c| + (rho + 2) A_c) + f0_c (|dk2| + u |k2|) + u |dz0_c|"""
+    if raw:
+        f0, f1 = f0.clamp_min(0.0), f1.clamp_min(0.0)
+    n, c, h, wd = f0.shape
+    hw = h * wd
+    wv = w.view(1, -1, 1, 1).double()
+    eps = 1e-10
+    r0, r1 = f0.pow(2).sum(1, keepdim=True).sqrt(), f1.pow(2).sum(1, keepdim=True).sqrt()
+    i0, i1 = 1.0 / (r0 + eps), 1.0 / (r1 + eps)
+    t = f0 * i0 - f1 * i1
+    A = f0 * i0 + f1 * i1
+    rho = c / 2 + 3
+    d = (wv * t * t).sum(1)
+    dd = U * (wv * (2 * (rho + 2) * A * t.abs() + (2 + c) * t * t)).sum(1)
+    value = coeff / hw * d.sum()
+    if workgroups is None:
+        workgroups = n * (((h + 2) * (wd + 2) + 31) // 32)
+    vbound = abs(coeff) / hw * (dd.sum() + (26 if addends is None else addends - 1) * U * d.sum()) + workgroups * 2.0 ** -41
+    S = (wv * t * f0).sum(1, keepdim=True)
+    ES = U * (wv * f0 * ((rho + 2) * A + (2 + c) * t.abs())).sum(1, keepdim=True)
+    g2 = 2.0 * grad_coeff / hw
+    k1 = g2 * i0
+    safe_r0 = torch.where(r0 > 0, r0, torch.ones_like(r0))
+    k2 = torch.where(r0 > 0, g2 * S * i0 * i0 / safe_r0, torch.zeros_like(r0))
+    dk2 = torch.where(r0 > 0, abs(g2) * i0 * i0 / safe_r0 * (ES + S.abs() * U * (2 * rho + c / 2 + 6)), torch.zeros_like(r0))
+    live = f0 > 0
+    dz = torch.where(live, k1 * wv * t - k2 * f0, torch.zeros_like(f0))
+    bound = U * k1.abs() * wv * ((rho + 5) * t.abs() + (rho + 2) * A) + f0 * (dk2 + U * k2.abs()) + U * dz.abs()
+    bound = torch.where(live, bound, torch.zeros_like(bound))
+    return value, vbound, dz, bound
+
+
+def lpips_layer(z0, z1, w, coeff, grad_coeff, workgroups, raw, exact_sum=False):
+    """vts_lpips_layer (fp32): "loss" = coeff sum_n mean_pixels sum_c w_c (f0n - f1n)^2, "dz0" = grad_coeff d(that sum) / d z0, through
+    lpips_layer_judge with K = N HW addends.  workgroups: N ceil(HW / 64) for the register kernels, N min(ceil(HW / 256), 2048) for the
+    generic one.  exact_sum (one-hot pixels of value 1.0, dyadic w: r = 1, 1 / (1 + 1e-10) = 1 in fp32, every d dyadic): the loss unit is
+    the fixed-point rounding alone (eps itself moves the float64 value by 2e-10 of it: below 1 % of that unit for |value| <= 0.04 N)."""
+    z0, z1 = _f64(z0), _f64(z1)
+    n, _, h, wd = z0.shape
+    value, vbound, dz, bound = lpips_layer_judge(z0, z1, _f64(w), _f32(coeff), _f32(grad_coeff), workgroups=workgroups, raw=raw, addends=n * h * wd)
+    if exact_sum:
+        vbound = workgroups * 2.0 ** -41
+    return {"loss": (value.reshape(1), torch.as_tensor(vbound, dtype=torch.float64).reshape(1)), "dz0": (dz + 0.0, bound)}

@@ -9,12 +9,14 @@
                    autograd on oracle.perceptual.LPIPS to 1e-12).  Biases, the LPIPS arithmetic, the pooling (a selection) and the final
                    input gradient stay float64.
   conv_judge       float64 reference, absref and the derived bound of one vts_conv3x3_bf16 launch
-  lpips_layer_judge  the same for vts_lpips_layer_bf16
+  lpips_layer_judge  the same for vts_lpips_layer_bf16 (it lives in oracle/launch_ref.py, beside the judges of the fp32 head)
 """
 import math
 
 import torch
 import torch.nn.functional as F
+
+from oracle.launch_ref import lpips_layer_judge  # noqa: F401  (the bf16 tests call it as R.lpips_layer_judge)
 
 U = 2.0 ** -24          # fp32 unit roundoff
 UB = 2.0 ** -8          # bf16: 8 significant bits, so half an ulp is at most 2^-8 of the value
@@ -78,48 +80,7 @@ def ratio(got, ref, bound):
     return float(r.max())
 
 
-# ---- the LPIPS head of one tap ----------------------------------------------------------------------------------------------------------------
-def lpips_layer_judge(f0, f1, w, coeff, grad_coeff):
-    """f0, f1 [N, C, H, W] >= 0 (bf16-exact, float64), w [C].  Returns value (float64 scalar: what the call adds to the slot), its bound,
-    dz0 [N, C, H, W] and its fp32 bound (the bf16 store adds 2^-8 |dz0|).
-
-    The unit is a derived linear rounding count, as oracle/launch_ref.py derives its own ((r + K) u absref): nothing in it is measured.
-      s = sum_c f^2 (C positive terms, any order)          relative error <= C u
-      r = sqrt(s), r + eps, i = 1 / (r + eps)               rho = C / 2 + 3 roundings on i (sqrt, add, divide: one each, correctly rounded)
-      t_c = f0_c i0 - f1_c i1                               |dt_c| <= (rho + 2) u A_c, A_c = f0_c i0 + f1_c i1 (two products, one subtraction)
-      d = sum_c w_c t_c^2                                   |dd| <= u sum_c w_c (2 (rho + 2) A_c |t_c| + (2 + C) t_c^2)
-      value = coeff / HW sum_pixels d                       + 26 u per term for the thread / wave / workgroup sums (<= 16 + 6 + 4 additions on any term's path)
-                                                            + 2^-41 per workgroup (its rounding to the fixed-point slot)
-      S = sum_c w_c t_c f0_c                                E_S = u sum_c w_c f0_c ((rho + 2) A_c + (2 + C) |t_c|)
-      k1 = 2 g / HW i0                                      rho + 3 roundings
-      k2 = 2 g / HW S i0^2 / r0                             |dk2| <= |2 g / HW| i0^2 / r0 (E_S + |S| u (2 rho + C / 2 + 6))
-      dz0_c = k1 w_c t_c - k2 f0_c where f0_c > 0           u |k1| w_c ((rho + 5) |t_c| + (rho + 2) A_c) + f0_c (|dk2| + u |k2|) + u |dz0_c|"""
-    n, c, h, wd = f0.shape
-    hw = h * wd
-    wv = w.view(1, -1, 1, 1).double()
-    eps = 1e-10
-    r0, r1 = f0.pow(2).sum(1, keepdim=True).sqrt(), f1.pow(2).sum(1, keepdim=True).sqrt()
-    i0, i1 = 1.0 / (r0 + eps), 1.0 / (r1 + eps)
-    t = f0 * i0 - f1 * i1
-    A = f0 * i0 + f1 * i1
-    rho = c / 2 + 3
-    d = (wv * t * t).sum(1)
-    dd = U * (wv * (2 * (rho + 2) * A * t.abs() + (2 + c) * t * t)).sum(1)
-    value = coeff / hw * d.sum()
-    workgroups = n * (((h + 2) * (wd + 2) + 31) // 32)
-    vbound = abs(coeff) / hw * (dd.sum() + 26 * U * d.sum()) + workgroups * 2.0 ** -41
-    S = (wv * t * f0).sum(1, keepdim=True)
-    ES = U * (wv * f0 * ((rho + 2) * A + (2 + c) * t.abs())).sum(1, keepdim=True)
-    g2 = 2.0 * grad_coeff / hw
-    k1 = g2 * i0
-    safe_r0 = torch.where(r0 > 0, r0, torch.ones_like(r0))
-    k2 = torch.where(r0 > 0, g2 * S * i0 * i0 / safe_r0, torch.zeros_like(r0))
-    dk2 = torch.where(r0 > 0, abs(g2) * i0 * i0 / safe_r0 * (ES + S.abs() * U * (2 * rho + c / 2 + 6)), torch.zeros_like(r0))
-    live = f0 > 0
-    dz = torch.where(live, k1 * wv * t - k2 * f0, torch.zeros_like(f0))
-    bound = U * k1.abs() * wv * ((rho + 5) * t.abs() + (rho + 2) * A) + f0 * (dk2 + U * k2.abs()) + U * dz.abs()
-    bound = torch.where(live, bound, torch.zeros_like(bound))
-    return value, vbound, dz, bound
+# ---- the LPIPS head of one tap: oracle/launch_ref.py:lpips_layer_judge (imported above; the fp32 head of csrc/vts_perceptual.hip is judged by it too)
 
 
 # ---- the whole term ---------------------------------------------------------------------------------------------------------------------------

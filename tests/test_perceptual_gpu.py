@@ -20,6 +20,11 @@ def _dev():
     return torch.device("cuda:0")
 
 
+# The four kernel-level tests below (pooling and its adjoint, the ReLU mask, the ReLU-L1, the LPIPS head) compare against autograd on dense
+# tensors.  tests/test_perceptual_glue_gpu.py judges the same entries per launch: kernel instance, every element against float64 or bitwise,
+# guard bands, unowned borders, chunk loops and second sweeps.
+
+
 def rel(a, b):
     a, b = a.detach().double().cpu(), b.detach().double().cpu()
     return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()

@@ -758,6 +758,7 @@ extern "C" int vts_zero_border(float* buf, int64_t NC, int H, int W, int pad, vo
     hipLaunchKernelGGL(zero_border_kernel, dim3(std::min(cdiv(per, 256), 64), nc), dim3(256), 0, (hipStream_t)stream, buf + c0 * PH * PW, PH, PW, pad);
   }
   VTS_CHECK_LAUNCH("vts_zero_border");
+  vts_set_kernel("zero_border_kernel");
   return VTS_OK;
 }
 

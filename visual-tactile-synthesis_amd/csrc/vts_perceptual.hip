@@ -439,6 +439,7 @@ extern "C" int vts_maxpool2_relu_pad(const float* z, int NC, int H, int W, int p
                        out + (int64_t)c0 * PH * PW, zpad);
   }
   VTS_CHECK_LAUNCH("vts_maxpool2_relu_pad");
+  vts_set_kernel("maxpool2_relu_pad_kernel");
   return VTS_OK;
 }
 
@@ -451,6 +452,7 @@ extern "C" int vts_maxpool3s2_relu_pad(const float* z, int NC, int H, int W, int
                        out + (int64_t)c0 * PH * PW);
   }
   VTS_CHECK_LAUNCH("vts_maxpool3s2_relu_pad");
+  vts_set_kernel("maxpool3s2_relu_pad_kernel");
   return VTS_OK;
 }
 
@@ -458,6 +460,7 @@ extern "C" int vts_s2d4_pad(const float* x, int N, int C, int H, int W, int pad,
   VTS_CHECK_ARG(x && out && N >= 1 && N <= 65535 && C >= 1 && H >= 1 && W >= 1 && pad >= 0 && OH >= 1 && OW >= 1, "vts_s2d4_pad: bad args");
   hipLaunchKernelGGL(s2d4_pad_kernel, dim3(blocks_1d((int64_t)C * 16 * OH * OW), N), dim3(256), 0, (hipStream_t)stream, x, C, H, W, pad, OH, OW, out);
   VTS_CHECK_LAUNCH("vts_s2d4_pad");
+  vts_set_kernel("s2d4_pad_kernel");
   return VTS_OK;
 }
 
@@ -476,6 +479,7 @@ extern "C" int vts_maxpool2_relu_bwd(const float* g, const float* z, int NC, int
                          g + (int64_t)c0 * (H / 2) * (W / 2), z + zo, H, W, gz + (int64_t)c0 * PH * PW, zpad, g2 ? g2 + zo : nullptr, pad);
   }
   VTS_CHECK_LAUNCH("vts_maxpool2_relu_bwd");
+  vts_set_kernel(H % 2 == 0 && W % 2 == 0 ? "maxpool2_relu_bwd_win_kernel" : "maxpool2_relu_bwd_kernel");
   return VTS_OK;
 }
 
@@ -489,6 +493,7 @@ extern "C" int vts_relu_mask_pad(const float* g, const float* g2, const float* z
                        g2 ? g2 + zo : nullptr, z + zo, H, W, pad, out + (int64_t)c0 * PH * PW, zpad);
   }
   VTS_CHECK_LAUNCH("vts_relu_mask_pad");
+  vts_set_kernel("relu_mask_pad_kernel");
   return VTS_OK;
 }
 
@@ -507,6 +512,8 @@ extern "C" int vts_lpips_layer(const float* z0, const float* z1, int N, int C, i
   else
     hipLaunchKernelGGL(lpips_layer_kernel, dim3(blocks_1d(HW), N), dim3(256), 0, st, z0, z1, C, HW, w, coeff, slot, dz0, grad_coeff, Wm, zpad);
   VTS_CHECK_LAUNCH("vts_lpips_layer");
+  vts_set_kernel(C == 64 ? "lpips_layer_regs_kernel<16,4>" : C == 128 ? "lpips_layer_regs_kernel<32,4>" : C == 256 ? "lpips_layer_regs_kernel<64,4>"
+                 : C == 512 ? "lpips_layer_regs_kernel<64,8>" : "lpips_layer_kernel");
   return VTS_OK;
 }
 
@@ -515,6 +522,7 @@ extern "C" int vts_l1_relu(const float* za, const float* zb, int64_t n, float co
   hipLaunchKernelGGL(l1_relu_kernel, dim3(blocks_1d(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, za, zb, n, coeff,
                      reinterpret_cast<long long*>(loss_slot), grad);
   VTS_CHECK_LAUNCH("vts_l1_relu");
+  vts_set_kernel("l1_relu_kernel");
   return VTS_OK;
 }
 
@@ -523,6 +531,7 @@ extern "C" int vts_lpips_input(const float* x, int64_t x_nstride, int N, int Cx,
   hipLaunchKernelGGL(lpips_input_kernel, dim3(blocks_1d(HW), N), dim3(256), 0, (hipStream_t)stream, x, x_nstride, HW, Cx, 1.f / scale3[0], 1.f / scale3[1],
                      1.f / scale3[2], -shift3[0] / scale3[0], -shift3[1] / scale3[1], -shift3[2] / scale3[2], y);
   VTS_CHECK_LAUNCH("vts_lpips_input");
+  vts_set_kernel("lpips_input_kernel");
   return VTS_OK;
 }
 
@@ -531,6 +540,7 @@ extern "C" int vts_lpips_input_bwd(const float* g, int N, int Cx, int HW, const 
   hipLaunchKernelGGL(lpips_input_bwd_kernel, dim3(blocks_1d(HW), N), dim3(256), 0, (hipStream_t)stream, g, HW, Cx, 1.f / scale3[0], 1.f / scale3[1],
                      1.f / scale3[2], dx, dx_nstride, accumulate);
   VTS_CHECK_LAUNCH("vts_lpips_input_bwd");
+  vts_set_kernel("lpips_input_bwd_kernel");
   return VTS_OK;
 }
 
@@ -545,6 +555,7 @@ extern "C" int vts_vgg_stack_input(const float* fake_I, int64_t fake_I_nstride, 
   hipLaunchKernelGGL(vgg_stack_input_kernel, dim3(blocks_1d(3 * ((int64_t)H + 2) * (W + 2)), 6 * N), dim3(256), 0, (hipStream_t)stream, fake_I, fake_I_nstride,
                      real_I, real_I_nstride, fake_T, fake_T_nstride, real_T, real_T_nstride, N, H, W, out);
   VTS_CHECK_LAUNCH("vts_vgg_stack_input");
+  vts_set_kernel("vgg_stack_input_kernel");
   return VTS_OK;
 }
 
@@ -563,5 +574,6 @@ extern "C" int vts_vgg_stack_input_bwd(const float* dx, int N, int H, int W, flo
     hipLaunchKernelGGL(vgg_stack_input_bwd_kernel<1>, dim3(blocks_1d(HW), N), dim3(256), 0, (hipStream_t)stream, dx, N, HW, d_fake_I, d_fake_I_nstride,
                        d_fake_T, d_fake_T_nstride, accumulate);
   VTS_CHECK_LAUNCH("vts_vgg_stack_input_bwd");
+  vts_set_kernel(v4 ? "vgg_stack_input_bwd_kernel<4>" : "vgg_stack_input_bwd_kernel<1>");
   return VTS_OK;
 }

@@ -13,91 +13,61 @@ The discriminators return one tensor, and the reference's GANLoss takes `input[-
 [N, 1, h, w] that is the map of the LAST SAMPLE.  Every GAN term of this model is therefore the loss of the batch's last prediction map
 (the other samples still reach it through the BatchNorm statistics); networks.GANLossLastSample restates that.
 Optimisers: G and D at `lr` with betas (beta1, 0.999), D2 at `lr_G2` with (beta1, beta2) (:281-286); the schedulers are BaseModel's.
+The step itself is PatchBaselineModel's (models/patch_baseline.py).
 """
 import os
 
 import torch
 
 from vts.misc import str2bool
-from vts import engine, metrics, ops
+from vts import engine, ops
 from vts.ops import Act
-from vts.optim import FlatAdam, FlatParams
+from vts.optim import FlatAdam
 
 from . import networks
 from .base_model import BaseModel
-from .sinskitG_model import add_model_flags
+from .patch_baseline import PatchBaselineModel, add_baseline_flags, set_phase_defaults
 
 B = str2bool
 
-# (flag, type, default)  -- reference: pix2pix_model.py:54-132
-MODEL_FLAGS = [
-    ("lambda_L1", float, 100.0), ("lr_G2", float, 0.0005), ("sketch_nc", int, 1), ("image_nc", int, 3), ("touch_nc", int, 2),
-    ("data_len", int, 200), ("center_w", int, 1280), ("center_h", int, 960), ("num_touch_patch_for_logging", int, 10),
-    ("use_bg_mask", B, True), ("T_resolution_multiplier", int, 1), ("padded_size", int, 1800), ("sample_bbox_per_patch", int, 2),
-    ("save_S_patch", B, False), ("save_T_concat_tensor", B, False), ("save_raw_arr_vis", B, False), ("scale_nz", float, 0.25),
-    ("return_patch", B, False),
-]
+# (flag, type, default) besides patch_baseline.COMMON_FLAGS  -- reference: pix2pix_model.py:54-132
+MODEL_FLAGS = [("return_patch", B, False)]
 
-LOSS_SLOTS = ["G_GAN", "G_L1", "D_real", "D_fake", "D2_real", "D2_fake", "G_GAN_I", "G_GAN_T"]
 RESNETS = ("resnet_6blocks", "resnet_9blocks")
 PATCHGANS = ("basic", "n_layers")
 
 
-class Pix2PixModel(BaseModel):
+class Pix2PixModel(PatchBaselineModel):
+    LOSS_SLOTS = ("G_GAN", "G_L1", "D_real", "D_fake", "D2_real", "D2_fake", "G_GAN_I", "G_GAN_T")
+    GAN_LOSS = networks.GANLossLastSample
+
     @staticmethod
     def modify_commandline_options(parser, is_train=True):
-        add_model_flags(parser, MODEL_FLAGS)
-        parser.add_argument("--use_hip_graph", type=B, default=True)   # not a reference flag: replay captured HIP graphs
-        # not reference flags: weight files of the optional metric networks (upstream downloads them) and --eval_T_FID (T_FID is known to
-        # compute_evaluation_metric but in none of upstream's metric lists)
-        metrics.add_metric_flags(parser)
+        add_baseline_flags(parser, MODEL_FLAGS)
         parser.set_defaults(norm="batch", netG="resnet_9blocks", dataset_mode="aligned", dataset="patchskit", crop_size=1536)
-        verbose_freq = 320
         if is_train:
-            parser.set_defaults(pool_size=0, gan_mode="vanilla", return_patch=True, batch_size=32, display_freq=verbose_freq,
-                                print_freq=verbose_freq, save_latest_freq=verbose_freq, validation_freq=verbose_freq, save_epoch_freq=50,
-                                display_id=0, save_raw_arr_vis=False)
-        else:
-            parser.set_defaults(return_patch=False, batch_size=1, save_S_patch=True, save_raw_arr_vis=False, sample_bbox_per_patch=1,
-                                data_len=1)
+            parser.set_defaults(pool_size=0, gan_mode="vanilla")
+        set_phase_defaults(parser, is_train, batch_size=32)
         return parser
 
-    def __init__(self, opt):
-        BaseModel.__init__(self, opt)
-        if not self.gpu_ids or not torch.cuda.is_available():
-            raise RuntimeError("Pix2PixModel runs on the MI355X HIP path only (no CPU fallback): pass --gpu_ids 0 on a GPU box")
-        self._check_unbuilt(opt)
-        self.test_edit_S = "edit" in opt.dataroot
-        self.loss_names, self.visual_names, self.model_names = self.name_lists(opt)
-        self.netG = networks.define_G(opt.sketch_nc, opt.image_nc + opt.touch_nc, opt.ngf, opt.netG, opt.norm, not opt.no_dropout,
-                                      opt.init_type, opt.init_gain, opt.no_antialias, opt.no_antialias_up, self.gpu_ids, opt)
-        self.flatG = FlatParams(self.netG)
-        if self.isTrain:
-            self.criterionGAN = networks.GANLossLastSample(opt.gan_mode)
-            self.netD = networks.define_D(opt.image_nc + opt.sketch_nc, opt.ndf, opt.netD, opt.n_layers_D, opt.norm, opt.init_type,
-                                          opt.init_gain, opt.no_antialias, gpu_ids=self.gpu_ids, opt=opt)
-            self.netD2 = networks.define_D(opt.touch_nc + opt.sketch_nc, opt.ndf, opt.netD, opt.n_layers_D, opt.norm, opt.init_type,
-                                           opt.init_gain, opt.no_antialias, gpu_ids=self.gpu_ids, opt=opt)
-            self.flatD, self.flatD2 = FlatParams(self.netD), FlatParams(self.netD2)
-            self.optimizer_G = FlatAdam(self.flatG, opt.lr, (opt.beta1, 0.999))
-            self.optimizer_D = FlatAdam(self.flatD, opt.lr, (opt.beta1, 0.999))
-            self.optimizer_D2 = FlatAdam(self.flatD2, opt.lr_G2, (opt.beta1, opt.beta2))
-            self.optimizers += [self.optimizer_G, self.optimizer_D, self.optimizer_D2]
-        self._loss_buf = ops.loss_slots(len(LOSS_SLOTS), self.device)     # int64 fixed point (order-independent accumulation)
-        self._slot = {n: self._loss_buf[i:i + 1] for i, n in enumerate(LOSS_SLOTS)}
-        self._bufs = {}
-        self._graphs = None
-        self._eager_steps_done = 0
-        self.ddp = None
+    def _define_G(self, opt):
+        return networks.define_G(opt.sketch_nc, opt.image_nc + opt.touch_nc, opt.ngf, opt.netG, opt.norm, not opt.no_dropout,
+                                 opt.init_type, opt.init_gain, opt.no_antialias, opt.no_antialias_up, self.gpu_ids, opt)
+
+    def _define_Ds(self, opt):
+        return [networks.define_D(nc + opt.sketch_nc, opt.ndf, opt.netD, opt.n_layers_D, opt.norm, opt.init_type, opt.init_gain,
+                                  opt.no_antialias, gpu_ids=self.gpu_ids, opt=opt) for nc in (opt.image_nc, opt.touch_nc)]
+
+    def _make_optimizers(self, opt):
+        return (FlatAdam(self.flatG, opt.lr, (opt.beta1, 0.999)), FlatAdam(self.flatD, opt.lr, (opt.beta1, 0.999)),
+                FlatAdam(self.flatD2, opt.lr_G2, (opt.beta1, opt.beta2)))
 
     @staticmethod
-    def name_lists(opt):
-        """(loss_names, visual_names, model_names), pix2pix_model.py:193-206: the loss names are listed in both phases"""
-        model_names = ["G", "D", "D2"] if opt.isTrain else ["G"]
-        visual_names = ["real_S", "M", "fake_I", "fake_gx", "fake_gy", "fake_N"]
-        if "edit" not in opt.dataroot:
-            visual_names.insert(2, "real_I")
-        return ["G_GAN", "G_L1", "D_real", "D_fake", "D2_real", "D2_fake"], visual_names, model_names
+    def loss_name_list(opt):
+        """pix2pix_model.py:193-206: the loss names are listed in both phases"""
+        return ["G_GAN", "G_L1", "D_real", "D_fake", "D2_real", "D2_fake"]
+
+    update_learning_rate = BaseModel.update_learning_rate      # (the reference keeps BaseModel's schedulers for this model)
 
     @staticmethod
     def _check_unbuilt(opt):
@@ -129,32 +99,11 @@ class Pix2PixModel(BaseModel):
         BaseModel.parallelize(self)
 
     # ------------------------------------------------------------------ input
-    def _drop_graphs(self):
-        if self._graphs is not None:
-            self._graphs = None
-            ops.release_ws((id(self), "train"))
-
-    def _load(self, name, host):
-        t = torch.as_tensor(host)
-        buf = self._bufs.get(name)
-        if buf is None or tuple(buf.shape) != tuple(t.shape):
-            buf = self._bufs[name] = torch.empty(tuple(t.shape), dtype=torch.float32, device=self.device)
-            self._drop_graphs()
-        buf.copy_(t.to(torch.float32), non_blocking=True)
-        return buf
-
     def set_input(self, input, phase="train", timing=False, verbose=False):
         """pix2pix_model.py:288-367.  Patches (return_patch): S_images / M_images / I_images [N, c, h, w], T_images [N, 2, h, w], I_masks
         [N, h, w].  Full images: S / M / I [N, c, H, W] with T_coords, full_T_coords and T_images [N, NT, 2, h, w], I_masks [N, NT, h, w]:
         the tactile patches are flattened to [N * NT, 2, h, w] and masked; the generator runs on the whole sketch."""
-        self.data_phase = phase
-        sk, mk, ik = ("S_images", "M_images", "I_images") if self.opt.return_patch else ("S", "M", "I")
-        S = self._load("S", input[sk])
-        self.M = self._load("M", input[mk])
-        self.name = input["name"]
-        self.image_paths = input["S_paths"]
-        self.augmentation_params = input.get("augmentation_params")
-        self.real_S = ops.mask_mul(S, self.M, out=S)
+        ik = self._set_sketch(input, phase)
         if self.test_edit_S:
             return
         I = self._load("I", input[ik])
@@ -177,118 +126,22 @@ class Pix2PixModel(BaseModel):
         self.real_T = ops.mask_mul(T, self.I_masks, out=T)
         self.real_gx, self.real_gy = self.real_T[:, 0:1], self.real_T[:, 1:2]
 
-    # ------------------------------------------------------------------ forward
-    def forward(self, keep=False):
-        n, _, h, w = self.real_S.shape
-        dev = self.device
-        g_out, self._g_ctx = engine.resnet_forward(self.netG, Act(self.real_S), keep=keep)
-        self.g_out = g_out
-        self.fake_I = torch.empty(n, 3, h, w, device=dev)
-        self.fake_T = torch.empty(n, 2, h, w, device=dev)
-        self.fake_N = torch.empty(n, 3, h, w, device=dev)
-        ops.g_post(g_out, self.M, self.opt.scale_nz, fake_I=self.fake_I, fake_T=self.fake_T, fake_N=self.fake_N)
-        self.fake_gx, self.fake_gy = self.fake_T[:, 0:1], self.fake_T[:, 1:2]
-
-    def test(self, timing=False):
-        with torch.no_grad():
-            self.forward(keep=False)
-
     # ------------------------------------------------------------------ training step
-    def _seg_forward_d(self):
-        """the step's ONE generator forward, then backward_D: both discriminators side by side (engine.msd_multi); per discriminator a fake
-        pass and a real pass, two BatchNorm batches in that order (pix2pix_model.py:399-418)"""
-        slot = self._slot
-        self._loss_buf.zero_()
-        self.forward(keep=True)
+    def _g_forward(self, keep):
+        return engine.resnet_forward(self.netG, Act(self.real_S), keep=keep)
 
-        def pair(fake, real, s_fake, s_real):
-            return [dict(in0=self.real_S, in1=fake, real=False, coeff=1.0, slot=slot[s_fake], grad_coeff=0.5),
-                    dict(in0=self.real_S, in1=real, real=True, coeff=1.0, slot=slot[s_real], grad_coeff=0.5, accumulate=True)]
-
-        engine.msd_multi([(self.netD, pair(self.fake_I, self.real_I, "D_fake", "D_real")),
-                          (self.netD2, pair(self.fake_T, self.real_T, "D2_fake", "D2_real"))], self.criterionGAN)
-
-    def _seg_adam_d_g(self):
-        slot, dev = self._slot, self.device
-        n, _, h, w = self.real_S.shape
-        self.optimizer_D.step(1.0)
-        self.optimizer_D2.step(1.0)
-        d_fake_I = torch.empty(n, 3, h, w, device=dev)
-        d_fake_T = torch.empty(n, 2, h, w, device=dev)
-        engine.msd_multi([(self.netD, [dict(in0=self.real_S, in1=self.fake_I, real=True, coeff=1.0, slot=slot["G_GAN_I"], grad_coeff=1.0,
-                                            param_grads=False, input_grad=(d_fake_I, False))]),
-                          (self.netD2, [dict(in0=self.real_S, in1=self.fake_T, real=True, coeff=1.0, slot=slot["G_GAN_T"], grad_coeff=1.0,
-                                             param_grads=False, input_grad=(d_fake_T, False))])], self.criterionGAN)
-        slot["G_GAN"].copy_(slot["G_GAN_I"] + slot["G_GAN_T"])
+    def _g_extra_terms(self, d_fake_I, d_fake_T):
         # (L1(fake_I, real_I) + L1(fake_T, real_T)) * lambda_L1, each a mean (:440-442): value into one slot, sign(.) added to the gradients
-        lam = self.opt.lambda_L1
+        lam, slot = self.opt.lambda_L1, self._slot
         ops.l1(self.fake_I, self.real_I, lam / self.fake_I.numel(), slot["G_L1"], grad=d_fake_I, accumulate=True)
         ops.l1(self.fake_T, self.real_T, lam / self.fake_T.numel(), slot["G_L1"], grad=d_fake_T, accumulate=True)
-        d_raw = torch.empty(n, 5, h, w, device=dev)
-        ops.g_out_grad(d_fake_I, d_fake_T, self.M, self.g_out, d_raw)
+
+    def _g_backward(self, d_raw):
         engine.resnet_backward(self.netG, self._g_ctx, d_raw)
-
-    def _seg_adam_g(self):
-        self.optimizer_G.step(1.0)
-
-    def _segments(self):
-        return [self._seg_forward_d, self._seg_adam_d_g, self._seg_adam_g]
-
-    def _capture_graphs(self):
-        torch.cuda.synchronize()
-        pool = torch.cuda.graph_pool_handle()
-        stream = torch.cuda.Stream()
-        counts = [o.step_count for o in self.optimizers]
-        graphs, nodes = [], []
-        ops.freeze_ws((id(self), "train"))
-        try:
-            for seg in self._segments():
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=pool, stream=stream, capture_error_mode="thread_local"):
-                    seg()
-                    nodes.append(ops.capture_node_count())
-                graphs.append(g)
-        except Exception:
-            ops.release_ws((id(self), "train"))
-            raise
-        for o, c in zip(self.optimizers, counts):
-            o.step_count = c
-        self._graphs = graphs
-        self.graph_nodes = nodes
 
     def optimize_parameters(self, epoch=0, timing=False):
         real_T = getattr(self, "real_T", None)
         if real_T is None or tuple(real_T.shape[2:]) != tuple(self.real_S.shape[2:]) or real_T.shape[0] != self.real_S.shape[0]:
             raise ValueError("the training step runs on paired patches (--return_patch True): tactile %s against sketch %s"
                              % (None if real_T is None else tuple(real_T.shape), tuple(self.real_S.shape)))
-        for o in self.optimizers:
-            o.sync_lr()
-        use_graph = bool(getattr(self.opt, "use_hip_graph", False))
-        if use_graph and self._graphs is None and self._eager_steps_done >= 1:
-            self._capture_graphs()
-        replay = use_graph and self._graphs is not None
-        for i, seg in enumerate(self._segments()):
-            if replay:
-                self._graphs[i].replay()
-            else:
-                seg()
-        if replay:
-            for o in self.optimizers:
-                o.step_count += 1
-        else:
-            self._eager_steps_done += 1
-
-    # ------------------------------------------------------------------ logging
-    def get_current_losses(self):
-        vals = ops.loss_values(self._loss_buf)
-        for i, name in enumerate(LOSS_SLOTS):
-            setattr(self, "loss_" + name, vals[i])
-        return BaseModel.get_current_losses(self)
-
-    def compute_metrics(self, prefix=""):
-        """the evaluation metrics of the outputs of the last forward() / test() (pix2pix_model.py:572-590 -> compute_evaluation_metric):
-        vts/metrics.py, shared by the three baselines"""
-        return metrics.model_metrics(self, prefix)
-
-    def compute_visuals(self):
-        pass
+        self._run_step()

@@ -30,6 +30,7 @@ from vts.optim import FlatAdam, FlatParams
 
 from . import networks
 from .base_model import BaseModel
+from .graphed_step import GraphedStepModel
 
 B = str2bool
 
@@ -70,7 +71,8 @@ def add_model_flags(parser, table):
             parser.add_argument("--" + name, type=typ, default=default)
 
 
-class SinSKITGModel(BaseModel):
+class SinSKITGModel(GraphedStepModel):
+    LOSS_SLOTS = LOSS_SLOTS
     MODEL_NAME = "sinskitG"
     DATASET_MODE = "singleskit"
     DATAROOT = "./datasets/singleskit_FlowerShorts_padded_1800_x1/"
@@ -115,7 +117,7 @@ class SinSKITGModel(BaseModel):
 
     # ------------------------------------------------------------------ construction
     def __init__(self, opt):
-        BaseModel.__init__(self, opt)
+        GraphedStepModel.__init__(self, opt)
         if not self.gpu_ids or not torch.cuda.is_available():
             raise RuntimeError("%s runs on the MI355X HIP path only (no CPU fallback): pass --gpu_ids 0 on a GPU box"
                                % type(self).__name__)
@@ -238,20 +240,15 @@ class SinSKITGModel(BaseModel):
         self.loss_lpips_dtype = getattr(opt, "lpips_dtype", "fp32")       # the loss terms only; the I_LPIPS / T_LPIPS metrics run fp32
         if self.isTrain and (opt.lambda_G1_lpips > 0 or opt.lambda_G2_lpips > 0):
             self._lpips_net()
-        self._loss_buf = ops.loss_slots(len(LOSS_SLOTS), self.device)     # int64 fixed point (order-independent accumulation)
-        self._slot = {n: self._loss_buf[i:i + 1] for i, n in enumerate(LOSS_SLOTS)}
+        self._init_step_state()
         self._spe_cache = {}
-        self._bufs = {}         # persistent input buffers (stable addresses for captured HIP graphs)
         self._pins, self._pin_evt = {}, {}   # pinned staging buffers of pageable host inputs (see _load)
-        self._graphs = None     # the captured segments of the step, or None
         self._chained = False   # the chained single-segment schedule is in use (set by _segments)
         self._d2_lane = None
         self._infer_graph, self._infer_eager_done = None, False   # captured inference forward (test())
-        self._eager_steps_done = 0
         if engine.KO_LANES and tune.get("VTS_KO_LANES_ACK", "") != "timing-only":
             raise RuntimeError("VTS_KO_LANES skips discriminator lanes (wrong losses and gradients): set VTS_KO_LANES_ACK=timing-only to run the timing experiment")
         self._draws = None      # tests / parity runs inject {"aug": [4,N], "more_idx": [N,K]}
-        self.ddp = None
         self.style_code = None
 
     @staticmethod
@@ -1144,18 +1141,10 @@ class SinSKITGModel(BaseModel):
         return [(self._seg_d_updates, (), ("D", "D2")), (self._seg_g_pre, (), ()), (self._seg_g_main, ("D", "D2"), ("G",)),
                 (self._seg_adam_g, ("G",), ())]
 
-    def _comm(self, name, start):
-        if self.ddp is None or name not in self.ddp.buckets:
-            return
-        b = self.ddp.buckets[name]
-        b.start() if start else b.wait()
-
     def _drop_graphs(self):
         self._infer_graph, self._infer_eager_done = None, False
         ops.release_ws((id(self), "infer"))
-        if getattr(self, "_graphs", None) is not None:
-            self._graphs = None
-            ops.release_ws((id(self), "train"))
+        GraphedStepModel._drop_graphs(self)
 
     _INFER_OUTPUTS = ("g_out", "fake_I", "fake_T", "fake_N", "fake_gx", "fake_gy", "aug_fake_I", "aug_real_I", "_full_stack", "_g_ctx")
 
@@ -1163,32 +1152,19 @@ class SinSKITGModel(BaseModel):
                      "_fake_stack", "_real_stack", "_more_stack", "fake_T_concat", "pred_fake_I", "pred_fake_T_full", "_g_ctx",
                      "fake_sample_offset_x", "fake_sample_offset_y")
 
-    def _capture_graphs(self):
-        """Capture the segments as HIP graphs sharing one memory pool (torch.cuda.CUDAGraph over
-        the launch stream our ctypes kernels use).  Capturing records work without executing it."""
-        torch.cuda.synchronize()
-        pool = torch.cuda.graph_pool_handle()
-        stream = torch.cuda.Stream()
-        counts = [o.step_count for o in self.optimizers]
-        graphs, nodes = [], []
-        ops.freeze_ws((id(self), "train"))
-        try:
-            for seg, _, _ in self._segments():
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=pool, stream=stream, capture_error_mode="thread_local"):   # RCCL's watchdog thread queries events meanwhile
-                    seg()
-                    nodes.append(ops.capture_node_count())      # (all nodes, kernel nodes) of this segment: the replayed launch count
-                graphs.append(g)
-        except Exception:
-            ops.release_ws((id(self), "train"))
-            raise
-        for o, c in zip(self.optimizers, counts):
-            o.step_count = c   # host mirrors moved during capture; the device counters did not
-        self._graphs = graphs
-        self.graph_nodes = nodes
+    def _may_use_graphs(self):
+        return GraphedStepModel._may_use_graphs(self) and self._draws is None
+
+    def _after_capture(self):
         # the tensors the captured step writes (visuals, predictions, patch stacks): a validation test() in between rebinds these
         # attributes to ITS outputs, so every replay re-attaches the training ones (get_current_visuals / compute_metrics('train_'))
         self._graph_attrs = {k: getattr(self, k) for k in self._STEP_OUTPUTS if hasattr(self, k)}
+
+    def _after_step(self, replay, use_graph):
+        if replay:
+            self.__dict__.update(self._graph_attrs)
+        elif not use_graph:
+            self._g_ctx = None
 
     def optimize_parameters(self, epoch=0, timing=False):
         if self.train_set is None:
@@ -1204,30 +1180,8 @@ class SinSKITGModel(BaseModel):
                 except OSError as e:
                     print("could not write the 'latest' checkpoint before stopping: %s" % e, flush=True)
             raise
-        self._gscale = self.ddp.grad_scale if self.ddp is not None else 1.0
-        for o in self.optimizers:
-            o.sync_lr()
         self._prepare_ranks()
-        use_graph = bool(getattr(self.opt, "use_hip_graph", False)) and self._draws is None
-        if use_graph and self._graphs is None and self._eager_steps_done >= 1:
-            self._capture_graphs()
-        replay = use_graph and self._graphs is not None
-        for i, (seg, wait_for, start_after) in enumerate(self._segments()):
-            for nme in wait_for:
-                self._comm(nme, start=False)
-            if replay:
-                self._graphs[i].replay()
-            else:
-                seg()
-            for nme in start_after:
-                self._comm(nme, start=True)
-        if replay:
-            self.__dict__.update(self._graph_attrs)
-            for o in self.optimizers:
-                o.step_count += 1
-        else:
-            self._eager_steps_done += 1
-            self._g_ctx = None if not use_graph else self._g_ctx
+        self._run_step()
 
     # ------------------------------------------------------------------ evaluation metrics
     METRICS = ("I_PSNR", "T_AE", "T_MSE", "I_SSIM")
@@ -1296,11 +1250,8 @@ class SinSKITGModel(BaseModel):
 
     # ------------------------------------------------------------------ logging
     def get_current_losses(self):
-        vals = ops.loss_values(self._loss_buf)   # the only device->host sync of the loss path
         self._check_candidate_counts(wait=True)
-        for i, name in enumerate(LOSS_SLOTS):
-            setattr(self, "loss_" + name, vals[i])
-        return BaseModel.get_current_losses(self)
+        return GraphedStepModel.get_current_losses(self)
 
     def compute_visuals(self):
         pass

@@ -1,8 +1,10 @@
 """Float64 judge of the C ABI's conv / weight-gradient / normalisation semantics, of the step's glue kernels (loss, optimiser,
 pyramid, patches, post-processing, augmentation, staging, sampler) and of the padding / resampling / FIR operators (pad, blur, weight taps,
 table resampling, upfirdn2d, bias_act, nearest, tanh_bwd; their units are derived rounding counts, see that section) and of the fp32 glue of
-the perceptual terms (pooling, masks, the LPIPS head, the ReLU-L1, input scaling and stacking: the last section), written from the
-formulas in include/vts.h (not from the kernels).  Checker only: the product never imports it.
+the perceptual terms (pooling, masks, the LPIPS head, the ReLU-L1, input scaling and stacking) and of the kernels that carry the style and
+segmentation conditioning (SPADE modulate, eval statistics and spectral norm, AdaIN, the style bias and mapping Linear, the modconv
+reductions: the last section, judged by tests/test_style_kernels_gpu.py on the table tests/style_kernel_cases.py, itself checked on the CPU
+by tests/test_style_kernel_cases.py), written from the formulas in include/vts.h (not from the kernels).  Checker only: the product never imports it.
 
 Every function returns {name: (ref, unit)} with float64 tensors: `ref` the exact value, `unit` the elementwise error scale of an
 fp32 evaluation, u * sqrt(K) * absref, where u = 2^-24, K is the number of products summed into the element and absref is the same
@@ -1411,3 +1413,345 @@ def lpips_layer(z0, z1, w, coeff, grad_coeff, workgroups, raw, exact_sum=False):
     if exact_sum:
         vbound = workgroups * 2.0 ** -41
     return {"loss": (value.reshape(1), torch.as_tensor(vbound, dtype=torch.float64).reshape(1)), "dz0": (dz + 0.0, bound)}
+
+
+# ---- style and segmentation conditioning (csrc/vts_spade.hip: modulate, eval statistics, spectral norm; csrc/vts_style.hip: AdaIN;
+# csrc/vts_style_levels.hip: the 16-class style bias and the mapping Linear; the six vts_modconv_* entries of csrc/vts_stylegan2.hip) --------
+# Units are derived rounding counts as in the resample section, (r + K) u absref, with two additions.
+#
+# Special functions.  `/`, sqrtf and rsqrtf get a constant each, measured as TANH_E was: worst |f32 - f64| / (u |f64|) of PyTorch's own
+# device kernels on the MI355X over 2^23 log-uniform arguments each (profiles/r22_style_kernels_parity.txt):
+#   torch.div    0.9996 at -1.30125928 / -5.204319   (both operands +-[1e-6, 1e6])
+#   torch.sqrt   1.0000 at 16777218                  ([1e-12, 1e8])
+#   torch.rsqrt  1.0000 at 0.000244140596            ([1e-12, 1e8]; 0.9999 at 0.000976559124 over [1e-6, 64])
+# The ROCm installation carries no document that states a bound for them.  The bound allows twice the measured worst plus 2 (one ulp is
+# <= 2 u |ref|): the library's own expansion and PyTorch's kernel may differ.
+DIV_E_MEASURED, SQRT_E_MEASURED, RSQRT_E_MEASURED = 0.9996, 1.0000, 1.0000
+DIV_E, SQRT_E, RSQRT_E = 2 * DIV_E_MEASURED + 2, 2 * SQRT_E_MEASURED + 2, 2 * RSQRT_E_MEASURED + 2
+#
+# Statistics computed inside a call (AdaIN's means and stds, the demodulation sum, the group means of the modulate backward, sum(g v)).
+# Every formula below is written once over values that carry (ref, unit) (class _V): an input is exact (unit 0); each operation gives the
+# float64 result, propagates its operands' units to first order through the absolute partial derivatives and adds its own rounding:
+#   a + b: ua + ub + u |a + b|          a * b: ua |b| + |a| ub + u |a b|          a / b: ua / |b| + |a| ub / b^2 + DIV_E u |a / b|
+#   sqrt a: ua / (2 sqrt a) + SQRT_E u sqrt a      rsqrt a: ua rsqrt a / (2 a) + RSQRT_E u rsqrt a      tanh: ua (1 - tanh^2) + TANH_E u |tanh|
+#   sum of K terms: sum of their units + (K - 1) u sum |term|  (any order: each term passes through at most K - 1 adds)
+#   times an exact factor (a 0 / 1 mask, the selection of a class): nothing;  times the LeakyReLU slope: one rounding where it applies
+# A fused multiply-add has one rounding fewer than the two operations counted.  The products of units dropped are second order in u: the
+# tests allow 1.01, and no family needs more: the largest relative unit of an intermediate is that of x - mean on the offset row of AdaIN,
+# about (m - 1) 100 u < 1e-3 for m = 129, so the dropped products stay below 0.1 % of a unit.
+# Where an output of a call is a function of another output of the same call (spectral norm: v, u, sigma, w / sigma; its backward: the
+# total, then dw) each stage is a function of its own: the first takes the inputs, the later ones take the value the call stored for the
+# earlier output (read back, exact), so a wrong element in any stage fails that stage.
+# Every formula also runs on any other arithmetic `A` (the fp32 one of tests/test_style_kernel_cases.py): A(tensor) lifts an exact input.
+class _V:
+    __slots__ = ("ref", "unit")
+
+    def __init__(self, ref, unit=None):
+        self.ref, self.unit = ref, (torch.zeros_like(ref) if unit is None else unit)
+
+    @staticmethod
+    def lift(t):
+        return _V(_f64(t))
+
+    @property
+    def val(self):
+        return self.ref
+
+    @staticmethod
+    def _co(o):
+        return o if isinstance(o, _V) else _V(torch.tensor(_f32(o), dtype=torch.float64))
+
+    def __add__(self, o):
+        o = _V._co(o)
+        r = self.ref + o.ref
+        return _V(r, self.unit + o.unit + U * r.abs())
+
+    __radd__ = __add__
+
+    def __sub__(self, o):
+        o = _V._co(o)
+        r = self.ref - o.ref
+        return _V(r, self.unit + o.unit + U * r.abs())
+
+    def __mul__(self, o):
+        o = _V._co(o)
+        r = self.ref * o.ref
+        return _V(r, self.unit * o.ref.abs() + self.ref.abs() * o.unit + U * r.abs())
+
+    __rmul__ = __mul__
+
+    def __truediv__(self, o):
+        o = _V._co(o)
+        r = self.ref / o.ref
+        return _V(r, self.unit / o.ref.abs() + self.ref.abs() * o.unit / (o.ref * o.ref) + DIV_E * U * r.abs())
+
+    def __rtruediv__(self, o):
+        return _V._co(o) / self
+
+    def sqrt(self):
+        r = self.ref.sqrt()
+        return _V(r, self.unit / (2 * r) + SQRT_E * U * r)
+
+    def rsqrt(self):
+        r = self.ref.rsqrt()
+        return _V(r, self.unit * r / (2 * self.ref.abs()) + RSQRT_E * U * r)
+
+    def tanh(self):
+        r = self.ref.tanh()
+        return _V(r, self.unit * (1 - r * r) + TANH_E * U * r.abs())
+
+    def sum(self, dim, keep=False, cnt=None):
+        """cnt: the number of terms that are not structural zeros (default: all of them)"""
+        dim = (dim,) if isinstance(dim, int) else tuple(dim)
+        n = math.prod(self.ref.shape[d] for d in dim) if cnt is None else cnt
+        n = torch.as_tensor(n, dtype=torch.float64)
+        return _V(self.ref.sum(dim, keepdim=keep), self.unit.sum(dim, keepdim=keep) + U * (n - 1).clamp_min(0) * self.ref.abs().sum(dim, keepdim=keep))
+
+    def clamp_min(self, c):
+        return _V(self.ref.clamp_min(c), torch.where(self.ref > c, self.unit, torch.zeros_like(self.unit)))
+
+    def mask(self, m):
+        """times an exact 0 / 1 factor"""
+        m = m.to(torch.float64)
+        return _V(self.ref * m, self.unit * m)
+
+    def slope(self, f, rounds):
+        """times the per-element factor f (1 or the fp32 slope); rounds: where that product rounds"""
+        f = f.to(torch.float64)
+        r = self.ref * f
+        return _V(r, self.unit * f.abs() + U * rounds.to(torch.float64) * r.abs())
+
+    def map(self, fn):
+        """data movement (view, index, permute, pad with zeros)"""
+        return _V(fn(self.ref), fn(self.unit))
+
+
+def _pack(d, A):
+    """{name: (ref, unit)} of the judge; the plain values under another arithmetic"""
+    return {k: ((v.ref, v.unit) if A is None else v.val) for k, v in d.items()}
+
+
+def _lrelu_factor(t, act):
+    """(factor, where it rounds) of act'(t) for VTS_ACT_NONE / VTS_ACT_LRELU"""
+    neg = ~(t.val > 0) if act == 1 else torch.zeros_like(t.val, dtype=torch.bool)
+    return torch.where(neg, torch.full_like(t.val, SLOPE32[1]), torch.ones_like(t.val)), neg
+
+
+def _planes(A, stat, n, c):
+    return A(stat.reshape(n, c, 1, 1))
+
+
+def _pad_zero(pad):
+    return (lambda t: torch.nn.functional.pad(t, (pad,) * 4)) if pad else (lambda t: t)
+
+
+def spade_modulate(x, mean, rstd, gamma, beta, act, out_pad=0, A=None):
+    """vts_spade_modulate: out = act((x - mean) rstd (1 + gamma) + beta), x [N, C, H, W], mean / rstd [N C]; out_pad: inside a zero border
+    (unit 0 there; the test compares the border bitwise with +0)"""
+    L = A or _V.lift
+    n, c = x.shape[:2]
+    t = (L(x) - _planes(L, mean, n, c)) * _planes(L, rstd, n, c) * (1.0 + L(gamma)) + L(beta)
+    return _pack({"out": t.slope(*_lrelu_factor(t, act)).map(_pad_zero(out_pad))}, A)
+
+
+def spade_modulate_bwd(g, x, mean, rstd, gamma, beta, mode, act, A=None):
+    """vts_spade_modulate_bwd on the dense interior of g: dgamma = g' xhat, dbeta = g', h = g' (1 + gamma);
+    mode 0 / 1: dx = rstd ((h - mean_G h) - (xhat - mean_G xhat) mean_G(h xhat)), G = the plane / the channel over the batch; mode 2: dx = rstd h"""
+    L = A or _V.lift
+    n, c, hh, ww = x.shape
+    r = _planes(L, rstd, n, c)
+    xh = (L(x) - _planes(L, mean, n, c)) * r
+    ga = 1.0 + L(gamma)
+    gp = L(g).slope(*_lrelu_factor(xh * ga + L(beta), act))
+    h = gp * ga
+    out = {"dgamma": gp * xh, "dbeta": gp}
+    if mode == 2:
+        out["dx"] = h * r
+    else:
+        dims, cnt = ((2, 3), float(hh * ww)) if mode == 0 else ((0, 2, 3), float(n) * float(hh * ww))
+        a, b, e = h.sum(dims, keep=True) / cnt, (h * xh).sum(dims, keep=True) / cnt, xh.sum(dims, keep=True) / cnt
+        out["dx"] = r * ((h - a) - (xh - e) * b)
+    return _pack(out, A)
+
+
+def spade_eval_stats(running_mean, running_var, eps, n, A=None):
+    """vts_spade_eval_stats: "mean" the running mean repeated over the batch (data movement, bitwise), "rstd" = 1 / sqrt(running_var + eps)"""
+    L = A or _V.lift
+    rep = lambda t: t.reshape(1, -1).repeat(n, 1).reshape(-1)
+    return _pack({"mean": L(running_mean).map(rep), "rstd": (1.0 / (L(running_var) + eps).sqrt()).map(rep)}, A)
+
+
+def _unit_vector(t, eps):
+    return t / (t * t).sum(0).sqrt().clamp_min(_f32(eps))
+
+
+def spectral_norm_v(w, u, eps, A=None):
+    """stage 1 of vts_spectral_norm (training): v = W^T u / max(|W^T u|, eps) from the inputs; w [Co, K]"""
+    L = A or _V.lift
+    return _pack({"v": _unit_vector((L(w) * L(u.reshape(-1, 1))).sum(0), eps)}, A)
+
+
+def spectral_norm_u(w, v, eps, A=None):
+    """stage 2: u = W v / max(|W v|, eps) at the v the call stored"""
+    L = A or _V.lift
+    return _pack({"u": _unit_vector((L(w) * L(v.reshape(1, -1))).sum(1), eps)}, A)
+
+
+def spectral_norm_sigma(w, u, v, A=None):
+    """stage 3: sigma = u^T W v at the stored (training) or given u, v"""
+    L = A or _V.lift
+    return _pack({"sigma": (L(u) * (L(w) * L(v.reshape(1, -1))).sum(1)).sum(0, keep=True)}, A)
+
+
+def spectral_norm_scale(w, sigma, A=None):
+    """stage 4: w_out = w / sigma at the stored sigma"""
+    L = A or _V.lift
+    return _pack({"w_out": L(w) / L(sigma.reshape(1, 1))}, A)
+
+
+def spectral_norm_bwd_total(g, w_sn, A=None):
+    """stage 1 of vts_spectral_norm_bwd: <g, w_sn>"""
+    L = A or _V.lift
+    return _pack({"total": (L(g) * L(w_sn)).sum((0, 1)).map(lambda t: t.reshape(1))}, A)
+
+
+def spectral_norm_bwd_dw(g, total, u, v, sigma, dw0=None, A=None):
+    """stage 2: dw (+)= (g - total u v^T) / sigma at the total the call stored"""
+    L = A or _V.lift
+    val = (L(g) - L(total.reshape(1, 1)) * L(u.reshape(-1, 1)) * L(v.reshape(1, -1))) / L(sigma.reshape(1, 1))
+    return _pack({"dw": val if dw0 is None else L(dw0) + val}, A)
+
+
+def _group_stats(p, m, eps):
+    mean = p.sum(1, keep=True) / float(m)
+    d = p - mean
+    return mean, ((d * d).sum(1, keep=True) / float(m - 1) + eps).sqrt()
+
+
+def adain(x, s, eps, A=None):
+    """vts_adain: out = (x - mean x) / std x * std s + mean s per row of x, s [NC, HW]; std = sqrt(unbiased variance + eps)"""
+    L = A or _V.lift
+    px, ps = L(x), L(s)
+    (mx, sx), (ms, ss) = _group_stats(px, x.shape[1], eps), _group_stats(ps, x.shape[1], eps)
+    return _pack({"out": (px - mx) / sx * ss + ms}, A)
+
+
+def adain_bwd(g, x, s, eps, A=None):
+    """vts_adain_bwd: the gradients of vts_adain's output w.r.t. both operands, with xhat = (x - mean x) / std x, gm = mean g,
+    r = sum(g xhat) / (m - 1):  dx = std s / std x (g - gm - xhat r),  ds = gm + r (s - mean s) / std s"""
+    L = A or _V.lift
+    m = x.shape[1]
+    pg, px, ps = L(g), L(x), L(s)
+    (mx, sx), (ms, ss) = _group_stats(px, m, eps), _group_stats(ps, m, eps)
+    xh = (px - mx) / sx
+    gm, r = pg.sum(1, keep=True) / float(m), (pg * xh).sum(1, keep=True) / float(m - 1)
+    return _pack({"dx": ss / sx * (pg - gm - xh * r), "ds": gm + r * (ps - ms) / ss}, A)
+
+
+def tconv_taps(size):
+    """[size, 4] 0 / 1: kernel index k reaches output position o of ConvTranspose2d(4, stride 2, padding 1) from an input of size / 2
+    positions: o = 2 i + k - 1 for some 0 <= i < size / 2"""
+    o, k = torch.arange(size).view(-1, 1), torch.arange(4).view(1, -1)
+    i2 = o + 1 - k
+    return ((i2 % 2 == 0) & (i2 >= 0) & (i2 < size)).to(torch.float64)
+
+
+def style_bias(code, w, out0, act_out, A=None):
+    """vts_style_bias: out = act_out(out0 + ConvTranspose2d(4, 2, 1) of the tile of r = max(code, 0) with the style rows w [K, Cout, 4, 4]).
+    The tile is constant, so a position's term is the sum over the taps that reach it of V[n, co, tap] = sum_c r[n, c] w[c, co, tap]; the
+    positions with the same taps (the distinct rows of tconv_taps) share the value."""
+    L = A or _V.lift
+    n, k = code.shape
+    oh, ow = out0.shape[-2:]
+    V = (L(code.clamp_min(0).reshape(n, k, 1, 1, 1)) * L(w.reshape(1, k, -1, 4, 4))).sum(1)            # [N, Cout, 4, 4]
+    (ty, iy), (tx, ix) = [torch.unique(tconv_taps(s), dim=0, return_inverse=True) for s in (oh, ow)]
+    taps = ty.view(-1, 1, 4, 1) * tx.view(1, -1, 1, 4)                                                 # [classes y, classes x, 4, 4]
+    B = V.map(lambda t: t[:, :, None, None]).mask(taps).sum((4, 5), cnt=taps.sum((2, 3)))              # [N, Cout, classes y, classes x]
+    t = L(out0) + B.map(lambda t: t[:, :, iy][:, :, :, ix])
+    return _pack({"out": t.tanh() if act_out == 3 else t}, A)
+
+
+def style_bias_bwd(g, code, k_cout, dw0=None, A=None):
+    """vts_style_bias_bwd: dw[c, co, ky, kx] (+)= sum_n r[n, c] S[n, co, ky, kx], S = the sum of g over the positions the tap reaches"""
+    L = A or _V.lift
+    n, k = code.shape
+    oh, ow = g.shape[-2:]
+    my, mx = tconv_taps(oh), tconv_taps(ow)
+    sx = L(g).map(lambda t: t[..., None]).mask(mx).sum(3, cnt=mx.sum(0))                               # [N, Cout, OH, 4 (kx)]
+    S = sx.map(lambda t: t[:, :, :, None, :]).mask(my.view(oh, 4, 1)).sum(2, cnt=my.sum(0).view(4, 1))  # [N, Cout, 4, 4]
+    val = (L(code.clamp_min(0).reshape(n, k, 1, 1, 1)) * S.map(lambda t: t[:, None])).sum(0)
+    return _pack({"dw": val if dw0 is None else L(dw0) + val}, A)
+
+
+def style_linear(x, w, A=None):
+    """vts_style_linear: z[n, p] = sum_k x[n, k] w[p, k]"""
+    L = A or _V.lift
+    return _pack({"z": (L(x[:, None, :]) * L(w[None])).sum(2)}, A)
+
+
+def style_linear_bwd(dz, x, w, dw0=None, want_dx=True, A=None):
+    """vts_style_linear_bwd: dw[p, k] (+)= sum_n dz[n, p] x[n, k];  dx[n, k] = sum_p dz[n, p] w[p, k]"""
+    L = A or _V.lift
+    val = (L(dz[:, :, None]) * L(x[:, None, :])).sum(0)
+    out = {"dw": val if dw0 is None else L(dw0) + val}
+    if want_dx:
+        out["dx"] = (L(dz[:, :, None]) * L(w[None])).sum(1)
+    return _pack(out, A)
+
+
+def modconv_demod(w, s, scale, eps, A=None):
+    """vts_modconv_demod: demod[n, co] = rsqrt(scale^2 sum_{ci, k} (w[co, ci, k] s[n, ci])^2 + eps), w [Cout, Cin, KK], s [N, Cin]"""
+    L = A or _V.lift
+    ws = L(w[None]) * L(s[:, None, :, None])
+    sc = L(torch.tensor(_f32(scale)))
+    return _pack({"demod": (sc * sc * (ws * ws).sum((2, 3)) + eps).rsqrt()}, A)
+
+
+def modconv_demod_bwd(dd, d, w, s, scale, dw0=None, ds0=None, A=None):
+    """vts_modconv_demod_bwd: q = dd (-1/2) d^3;  dw (+)= 2 scale^2 w sum_n q s^2;  ds (+)= 2 scale^2 s sum_co q sum_k w^2"""
+    L = A or _V.lift
+    pd, pw, ps = L(d), L(w), L(s)
+    q = L(dd) * -0.5 * pd * pd * pd                                                                    # [N, Cout]
+    sc = L(torch.tensor(_f32(scale)))
+    c2 = 2.0 * sc * sc
+    dw = c2 * pw * (q.map(lambda t: t[:, :, None, None]) * (ps * ps).map(lambda t: t[:, None, :, None])).sum(0)
+    ds = c2 * ps * (q.map(lambda t: t[:, :, None]) * (pw * pw).sum(2).map(lambda t: t[None])).sum(1)
+    return _pack({"dw": dw if dw0 is None else L(dw0) + dw, "ds": ds if ds0 is None else L(ds0) + ds}, A)
+
+
+def _wt(transpose):
+    """[Cout, Cin, KK] -> the stored layout ([Cin, Cout, KK] when transposed)"""
+    return (lambda t: t.transpose(0, 1).contiguous()) if transpose else (lambda t: t)
+
+
+def modconv_weight(w, scale, eps, transpose, A=None):
+    """vts_modconv_weight: wout = v d[co], v = scale w, d = rsqrt(sum_{ci, k} v^2 + eps)"""
+    L = A or _V.lift
+    v = _f32(scale) * L(w)
+    return _pack({"wout": (v * ((v * v).sum((1, 2), keep=True) + eps).rsqrt()).map(_wt(transpose))}, A)
+
+
+def modconv_weight_bwd(w, g, scale, eps, transpose, dw0=None, A=None):
+    """vts_modconv_weight_bwd: dw (+)= scale (d g - d^3 v sum(g v)), g in wout's layout"""
+    L = A or _V.lift
+    v, pg = _f32(scale) * L(w), L(_wt(transpose)(g))
+    d = ((v * v).sum((1, 2), keep=True) + eps).rsqrt()
+    val = _f32(scale) * (d * pg - d * d * d * v * (pg * v).sum((1, 2), keep=True))
+    return _pack({"dw": val if dw0 is None else L(dw0) + val}, A)
+
+
+def modconv_scale_dot(a, b, f, alpha, want_out, dot0=None, A=None):
+    """vts_modconv_scale_dot: out = a f[row] (when asked), dot[row] (+)= alpha sum_i a b; a, b [NC, HW]"""
+    L = A or _V.lift
+    val = _f32(alpha) * (L(a) * L(b)).sum(1)
+    out = {"dot": val if dot0 is None else L(dot0) + val}
+    if want_out:
+        out["out"] = L(a) * L(f.reshape(-1, 1))
+    return _pack(out, A)
+
+
+def modconv_transpose(w, out0=None, A=None):
+    """vts_modconv_transpose: out[ci, co, k] (+)= w[co, ci, k]; data movement without out0 (bitwise)"""
+    L = A or _V.lift
+    t = L(w).map(_wt(True))
+    return _pack({"out": t if out0 is None else L(out0) + t}, A)

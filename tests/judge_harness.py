@@ -1,5 +1,5 @@
-"""Guard-banded operands and the per-call judgement shared by tests/test_step_glue_gpu.py and tests/test_resample_gpu.py (each passes its
-own bounds and its own record of worst values).
+"""Guard-banded operands and the per-call judgement shared by tests/test_step_glue_gpu.py, tests/test_resample_gpu.py, tests/test_perceptual_glue_gpu.py
+and tests/test_style_kernels_gpu.py (each passes its own bounds and its own record of worst values).
 
 Every operand is a view (Op) inside a flat device buffer between BAND guard elements: NaN for floats, a sentinel for integers and bytes.
 Strided operands live in a larger NaN-filled tensor.  Outputs start NaN-filled, or seeded where the call accumulates.  judge() asserts, per
@@ -75,7 +75,8 @@ def execute(lib, call, opnds):
 
 def judge(lib, tag, expected, call, opnds, outs, bound, worst, per_family=False):
     """outs: (op, index or None, ref, unit, family): unit None: `ref` bitwise (in the output's dtype); ref None: scratch (owned, not
-    judged); an int64 op with a unit: a loss slot, judged as (slot - start) / 2^40.  bound: the constant C of |got - ref| <= C unit, or
+    judged); ref callable: called with stored(op) -> what this run left in an operand, it returns (ref, unit); an int64 op with a unit: a
+    loss slot, judged as (slot - start) / 2^40.  bound: the constant C of |got - ref| <= C unit, or
     {family: C}.  worst: kernel instance (per_family: (kernel instance, family)) -> [worst ratio, case, family, outputs judged], updated."""
     (kern, snap), (kern2, snap2) = execute(lib, call, opnds)
     assert kern == expected and kern2 == expected, "%s: ran %s, the table expects %s" % (tag, kern, expected)
@@ -90,6 +91,8 @@ def judge(lib, tag, expected, call, opnds, outs, bound, worst, per_family=False)
     for o, idx, ref, unit, fam in outs:
         if ref is None:
             continue
+        if callable(ref):            # a later stage of a staged call: (ref, unit) at what this run stored for the earlier outputs
+            ref, unit = ref(lambda p: p.content(snap[[q is p for q in opnds].index(True)]))
         if per_family:
             w = worst.setdefault((kern, fam), [0.0, tag, fam, 0])
         got = o.content(snap[[p is o for p in opnds].index(True)])

@@ -298,8 +298,9 @@ def claimed_instances():
     return c
 
 
-# kernels of the three sources judged elsewhere
-_MODCONV, _SPADE = "tests/test_modconv_style_gpu.py", "tests/test_spade_gpu.py"
+# kernels of the three sources judged elsewhere: elementwise by tests/test_style_kernels_gpu.py, whose table (tests/style_kernel_cases.py)
+# claims the instance strings their entries report
+_MODCONV = _SPADE = "tests/test_style_kernels_gpu.py"
 COVERED_ELSEWHERE = {k: _MODCONV for k in ("demod_kernel", "modw_kernel", "modw_bwd_kernel", "scale_dot_rows_kernel", "scale_dot_split_kernel",
                                            "scale_dot_finish_kernel", "demod_bwd_w_kernel", "demod_bwd_s_kernel", "wtranspose_kernel")}
 COVERED_ELSEWHERE.update({k: _SPADE for k in ("spade_mod_fwd_v4", "spade_mod_fwd_pad", "spade_mod_bwd_sums", "spade_mod_bwd_means", "spade_mod_bwd_apply",

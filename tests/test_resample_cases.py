@@ -9,6 +9,7 @@ import re
 import torch
 
 import resample_cases as T
+import style_kernel_cases
 from oracle import launch_ref as R
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "visual-tactile-synthesis_amd", "csrc")
@@ -66,8 +67,12 @@ def test_every_listed_entry_names_its_instance():
 
 def test_every_kernel_and_instance_of_the_sources_is_claimed_by_a_row():
     claimed = T.claimed_instances() | set(T.COVERED_ELSEWHERE)
-    unclaimed = [s for s in instance_strings() if s not in claimed]
-    assert not unclaimed, "instances without a row in tests/resample_cases.py: %s" % unclaimed
+    elsewhere = style_kernel_cases.claimed_instances()        # the strings of the entries whose kernels COVERED_ELSEWHERE lists
+    unclaimed = [s for s in instance_strings() if s not in claimed and s not in elsewhere]
+    assert not unclaimed, "instances without a row in tests/resample_cases.py or tests/style_kernel_cases.py: %s" % unclaimed
+    for s in instance_strings():
+        if s not in claimed:
+            assert style_kernel_cases.kernels_of(s) <= set(T.COVERED_ELSEWHERE), s
     names = {k for c in claimed for k in kernels_of(c)}
     missing = [k for k in global_kernels() if k not in names]
     assert not missing, "__global__ kernels without a row in tests/resample_cases.py: %s" % missing

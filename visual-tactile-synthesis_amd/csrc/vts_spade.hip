@@ -367,9 +367,11 @@ extern "C" int vts_spade_modulate(const float* x, const float* mean, const float
   if (out_pad == 0 && ((H * W) & 3) == 0 && aligned16(x, gamma, beta, out)) {
     const int64_t total4 = NC * (H * W / 4);
     hipLaunchKernelGGL(spade_mod_fwd_v4, dim3(flat_grid(total4)), dim3(256), 0, st, x, mean, rstd, gamma, beta, total4, H * W / 4, act, out);
+    vts_set_kernel("spade_mod_fwd_v4");
   } else {
     const int64_t total = NC * (H + 2 * out_pad) * (W + 2 * out_pad);
     hipLaunchKernelGGL(spade_mod_fwd_pad, dim3(flat_grid(total)), dim3(256), 0, st, x, mean, rstd, gamma, beta, total, H, W, out_pad, act, out);
+    vts_set_kernel("spade_mod_fwd_pad");
   }
   VTS_CHECK_LAUNCH("vts_spade_modulate");
   return VTS_OK;
@@ -381,6 +383,7 @@ extern "C" int vts_spade_eval_stats(const float* running_mean, const float* runn
   hipLaunchKernelGGL(spade_eval_stats_kernel, dim3((unsigned)cdiv64((int64_t)N * C, 256)), dim3(256), 0, (hipStream_t)stream, running_mean,
                      running_var, eps, N, C, mean, rstd);
   VTS_CHECK_LAUNCH("vts_spade_eval_stats");
+  vts_set_kernel("spade_eval_stats_kernel");
   return VTS_OK;
 }
 
@@ -399,21 +402,30 @@ extern "C" int vts_spade_modulate_bwd(const float* g, int g_pad, const float* x,
   const int frozen = mode == 2;
   hipStream_t st = (hipStream_t)stream;
   float *sums = ws, *means = ws ? ws + 3 * NC : nullptr;
-  if (H * W <= 1024)
+  const bool wave = H * W <= 1024;
+  if (wave)
     hipLaunchKernelGGL(spade_mod_bwd_sums<true>, dim3((unsigned)cdiv64(NC, 4)), dim3(256), 0, st, g, g_pad, x, mean, rstd, gamma, beta, NC, H, W, act,
                        frozen, dgamma, dbeta, dx, sums);
   else
     hipLaunchKernelGGL(spade_mod_bwd_sums<false>, dim3((unsigned)NC), dim3(256), 0, st, g, g_pad, x, mean, rstd, gamma, beta, NC, H, W, act, frozen,
                        dgamma, dbeta, dx, sums);
   VTS_CHECK_LAUNCH("vts_spade_modulate_bwd (sums)");
-  if (frozen) return VTS_OK;
+  if (frozen) {
+    vts_set_kernel(wave ? "spade_mod_bwd_sums<wave> frozen" : "spade_mod_bwd_sums<block> frozen");
+    return VTS_OK;
+  }
   hipLaunchKernelGGL(spade_mod_bwd_means, dim3((unsigned)cdiv64(NC, 256)), dim3(256), 0, st, sums, N, C, H * W, mode, means);
   VTS_CHECK_LAUNCH("vts_spade_modulate_bwd (means)");
-  if (((H * W) & 3) == 0 && aligned16(x, dx))
+  const bool v4 = ((H * W) & 3) == 0 && aligned16(x, dx);
+  if (v4)
     hipLaunchKernelGGL(spade_mod_bwd_apply_v4, dim3(flat_grid(NC * (H * W / 4))), dim3(256), 0, st, x, mean, rstd, means, NC, H * W / 4, dx);
   else
     hipLaunchKernelGGL(spade_mod_bwd_apply, dim3(flat_grid(NC * H * W)), dim3(256), 0, st, x, mean, rstd, means, NC, H * W, dx);
   VTS_CHECK_LAUNCH("vts_spade_modulate_bwd (apply)");
+  if (wave)
+    vts_set_kernel(v4 ? "spade_mod_bwd_sums<wave>+spade_mod_bwd_means+spade_mod_bwd_apply_v4" : "spade_mod_bwd_sums<wave>+spade_mod_bwd_means+spade_mod_bwd_apply");
+  else
+    vts_set_kernel(v4 ? "spade_mod_bwd_sums<block>+spade_mod_bwd_means+spade_mod_bwd_apply_v4" : "spade_mod_bwd_sums<block>+spade_mod_bwd_means+spade_mod_bwd_apply");
   return VTS_OK;
 }
 
@@ -477,12 +489,18 @@ extern "C" int vts_spectral_norm(const float* w, float* u, float* v, int Co, int
     hipLaunchKernelGGL(sn_v_kernel, dim3(1), dim3(1024), 0, st, part, RS, K, eps, v);
     VTS_CHECK_LAUNCH("vts_spectral_norm (v)");
   }
-  hipLaunchKernelGGL(sn_wv_kernel, dim3(Co), dim3(256), 0, st, w, v, K, (int)((K & 3) == 0 && aligned16(w, v)), s);
+  const int vec = (int)((K & 3) == 0 && aligned16(w, v));
+  hipLaunchKernelGGL(sn_wv_kernel, dim3(Co), dim3(256), 0, st, w, v, K, vec, s);
   VTS_CHECK_LAUNCH("vts_spectral_norm (W v)");
   hipLaunchKernelGGL(sn_sigma_kernel, dim3(1), dim3(1024), 0, st, s, Co, training, eps, u, sigma);
   VTS_CHECK_LAUNCH("vts_spectral_norm (sigma)");
   hipLaunchKernelGGL(sn_scale_kernel, dim3(flat_grid((int64_t)Co * K)), dim3(256), 0, st, w, sigma, (int64_t)Co * K, w_out);
   VTS_CHECK_LAUNCH("vts_spectral_norm (scale)");
+  if (training)
+    vts_set_kernel(vec ? "sn_wtu_kernel+sn_v_kernel+sn_wv_kernel<vec>+sn_sigma_kernel+sn_scale_kernel"
+                       : "sn_wtu_kernel+sn_v_kernel+sn_wv_kernel<scalar>+sn_sigma_kernel+sn_scale_kernel");
+  else
+    vts_set_kernel(vec ? "sn_wv_kernel<vec>+sn_sigma_kernel+sn_scale_kernel" : "sn_wv_kernel<scalar>+sn_sigma_kernel+sn_scale_kernel");
   return VTS_OK;
 }
 
@@ -498,5 +516,6 @@ extern "C" int vts_spectral_norm_bwd(const float* g, const float* w_sn, const fl
   const int gx = cdiv(K, 256) < 16 ? cdiv(K, 256) : 16;
   hipLaunchKernelGGL(sn_bwd_apply_kernel, dim3(gx, Co), dim3(256), 0, st, g, ws + Co, u, v, sigma, Co, K, dw, accumulate);
   VTS_CHECK_LAUNCH("vts_spectral_norm_bwd (apply)");
+  vts_set_kernel("sn_bwd_dot_kernel+sn_bwd_total_kernel+sn_bwd_apply_kernel");
   return VTS_OK;
 }

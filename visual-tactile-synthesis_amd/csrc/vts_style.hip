@@ -62,6 +62,7 @@ extern "C" int vts_adain(const float* x, const float* s, int NC, int HW, float e
   VTS_CHECK_ARG(x && s && out && NC >= 1 && HW >= 2, "vts_adain: bad args (unbiased variance needs HW >= 2)");
   hipLaunchKernelGGL(adain_fwd_kernel, dim3(cdiv(NC, 4)), dim3(256), 0, (hipStream_t)stream, x, s, NC, HW, eps, out);
   VTS_CHECK_LAUNCH("vts_adain");
+  vts_set_kernel("adain_fwd_kernel");
   return VTS_OK;
 }
 
@@ -69,5 +70,6 @@ extern "C" int vts_adain_bwd(const float* g, const float* x, const float* s, int
   VTS_CHECK_ARG(g && x && s && dx && ds && NC >= 1 && HW >= 2, "vts_adain_bwd: bad args");
   hipLaunchKernelGGL(adain_bwd_kernel, dim3(cdiv(NC, 4)), dim3(256), 0, (hipStream_t)stream, g, x, s, NC, HW, eps, dx, ds);
   VTS_CHECK_LAUNCH("vts_adain_bwd");
+  vts_set_kernel("adain_bwd_kernel");
   return VTS_OK;
 }

@@ -225,6 +225,7 @@ extern "C" int vts_style_bias(const float* code, int N, int K, const float* w, i
   const int gx = (int)min((int64_t)256, cdiv64((int64_t)OH * OW, 2048));
   hipLaunchKernelGGL(style_bias_apply_kernel, dim3(gx, N * Cout), dim3(256), 0, st, (const float*)ws, Cout, OH, OW, out, out_nstride, act_out);
   VTS_CHECK_LAUNCH("vts_style_bias (apply)");
+  vts_set_kernel("style_v_kernel+style_bias_apply_kernel");
   return VTS_OK;
 }
 
@@ -243,6 +244,7 @@ extern "C" int vts_style_bias_bwd(const float* g, int64_t g_nstride, const float
   VTS_CHECK_LAUNCH("vts_style_bias_bwd (dV)");
   hipLaunchKernelGGL(style_dw_kernel, dim3(cdiv(J, 256), K), dim3(256), 0, st, code, (const float*)dV, N, K, J, dw, accumulate);
   VTS_CHECK_LAUNCH("vts_style_bias_bwd (dW)");
+  vts_set_kernel("style_class_sums_kernel+style_dv_kernel+style_dw_kernel");
   return VTS_OK;
 }
 
@@ -256,6 +258,7 @@ extern "C" int vts_style_linear(const float* x, const float* w, int N, int K, in
   VTS_CHECK_ARG(N >= 1 && K >= 1 && P >= 1, "vts_style_linear: bad shape N %d K %d P %d", N, K, P);
   hipLaunchKernelGGL(style_linear_kernel, dim3(cdiv(P, 4)), dim3(256), 0, (hipStream_t)stream, x, w, N, K, P, z);
   VTS_CHECK_LAUNCH("vts_style_linear");
+  vts_set_kernel("style_linear_kernel");
   return VTS_OK;
 }
 
@@ -274,5 +277,6 @@ extern "C" int vts_style_linear_bwd(const float* dz, const float* x, const float
     hipLaunchKernelGGL(style_linear_dx_sum_kernel, dim3(cdiv(N * K, 256)), dim3(256), 0, st, (const float*)ws, N * K, chunks, dx);
     VTS_CHECK_LAUNCH("vts_style_linear_bwd (dx)");
   }
+  vts_set_kernel(dx ? "style_linear_dw_kernel+style_linear_dx_kernel+style_linear_dx_sum_kernel" : "style_linear_dw_kernel");
   return VTS_OK;
 }

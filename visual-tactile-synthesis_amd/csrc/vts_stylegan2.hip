@@ -424,6 +424,7 @@ extern "C" int vts_modconv_weight(const float* w, int Cout, int Cin, int KK, flo
   VTS_CHECK_ARG(w && wout && Cout >= 1 && Cin >= 1 && KK >= 1, "vts_modconv_weight: bad args");
   hipLaunchKernelGGL(modw_kernel, dim3(Cout), dim3(256), 0, (hipStream_t)stream, w, Cout, Cin, KK, scale, eps, transpose, wout);
   VTS_CHECK_LAUNCH("vts_modconv_weight");
+  vts_set_kernel("modw_kernel");
   return VTS_OK;
 }
 
@@ -432,6 +433,7 @@ extern "C" int vts_modconv_weight_bwd(const float* w, const float* g, int Cout, 
   VTS_CHECK_ARG(w && g && dw && Cout >= 1 && Cin >= 1 && KK >= 1, "vts_modconv_weight_bwd: bad args");
   hipLaunchKernelGGL(modw_bwd_kernel, dim3(Cout), dim3(256), 0, (hipStream_t)stream, w, g, Cout, Cin, KK, scale, eps, transpose, dw, accumulate);
   VTS_CHECK_LAUNCH("vts_modconv_weight_bwd");
+  vts_set_kernel("modw_bwd_kernel");
   return VTS_OK;
 }
 
@@ -440,6 +442,7 @@ extern "C" int vts_modconv_demod(const float* w, const float* s, int N, int Cout
   VTS_CHECK_ARG(w && s && demod && N >= 1 && Cout >= 1 && Cin >= 1 && KK >= 1, "vts_modconv_demod: bad args");
   hipLaunchKernelGGL(demod_kernel, dim3(Cout, N), dim3(256), 0, (hipStream_t)stream, w, s, Cout, Cin, KK, scale, eps, demod);
   VTS_CHECK_LAUNCH("vts_modconv_demod");
+  vts_set_kernel("demod_kernel");
   return VTS_OK;
 }
 
@@ -471,6 +474,8 @@ extern "C" int vts_modconv_scale_dot(const float* a, const float* b, const float
     else if (vec) hipLaunchKernelGGL((scale_dot_rows_kernel<64, true>), grid, dim3(256), 0, st, a, b, f, NC, hw, alpha, out, dot, accumulate);
     else hipLaunchKernelGGL((scale_dot_rows_kernel<64, false>), grid, dim3(256), 0, st, a, b, f, NC, hw, alpha, out, dot, accumulate);
     VTS_CHECK_LAUNCH("vts_modconv_scale_dot");
+    if (narrow) vts_set_kernel(vec ? "scale_dot_rows_kernel<16,vec>" : "scale_dot_rows_kernel<16,scalar>");
+    else vts_set_kernel(vec ? "scale_dot_rows_kernel<64,vec>" : "scale_dot_rows_kernel<64,scalar>");
     return VTS_OK;
   }
   const dim3 grid((unsigned)((int64_t)NC * S));
@@ -480,6 +485,9 @@ extern "C" int vts_modconv_scale_dot(const float* a, const float* b, const float
   if (S > 1) {
     hipLaunchKernelGGL(scale_dot_finish_kernel, dim3(cdiv(NC, 256)), dim3(256), 0, st, ws, NC, S, alpha, dot, accumulate);
     VTS_CHECK_LAUNCH("vts_modconv_scale_dot (finish)");
+    vts_set_kernel(vec ? "scale_dot_split_kernel<vec>+scale_dot_finish_kernel" : "scale_dot_split_kernel<scalar>+scale_dot_finish_kernel");
+  } else {
+    vts_set_kernel(vec ? "scale_dot_split_kernel<vec>" : "scale_dot_split_kernel<scalar>");
   }
   return VTS_OK;
 }
@@ -497,6 +505,7 @@ extern "C" int vts_modconv_demod_bwd(const float* dd, const float* d, const floa
   hipLaunchKernelGGL(demod_bwd_s_kernel, dim3(cdiv(Cin, 256 / KK), N), dim3(256), 0, (hipStream_t)stream, dd, d, w, s, Cout, Cin, KK, scale, ds,
                      accumulate_ds);
   VTS_CHECK_LAUNCH("vts_modconv_demod_bwd (ds)");
+  vts_set_kernel("demod_bwd_w_kernel+demod_bwd_s_kernel");
   return VTS_OK;
 }
 
@@ -507,5 +516,6 @@ extern "C" int vts_modconv_transpose(const float* w, int Cout, int Cin, int KK, 
   VTS_CHECK_ARG(cdiv64(total, 256) < (1ll << 31), "vts_modconv_transpose: weight too large");
   hipLaunchKernelGGL(wtranspose_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, (hipStream_t)stream, w, Cout, Cin, KK, out, accumulate);
   VTS_CHECK_LAUNCH("vts_modconv_transpose");
+  vts_set_kernel("wtranspose_kernel");
   return VTS_OK;
 }

@@ -671,7 +671,7 @@ int vts_g_post_stack(const float* g_out, const float* M, int N, int H, int W, fl
  *      't'  out[i, j] = x[i + pi0, j + pi1], zero outside          pi0 / pi1 = row / column translation (randint(-s, s + 1), s = int(extent / 8 + 0.5))
  *      'o'  rows clamp(pi0 - ch / 2 + [0, ch)), columns clamp(pi1 - cw / 2 + [0, cw)) zeroed, ch = int(H / 2 + 0.5), cw likewise
  *      'n'  out = x + pf * noise                                   pf = sigma (rand * 0.1, zeroed where the gate draw >= 0.5), noise [N, C, H, W] */
-int vts_diffaug_op_ws_floats(int N);
+int64_t vts_diffaug_op_ws_floats(int N);
 int vts_diffaug_op(const float* x, int64_t x_ns, float* out, int64_t out_ns, int N, int C, int H, int W, int op, const float* pf,
                    const int* pi0, const int* pi1, const float* noise, const float* M, float* ws, void* stream);
 

@@ -907,7 +907,7 @@ extern "C" int vts_g_out_grad(const float* d_fake_I, const float* d_fake_T, cons
   return vts_g_out_grad_pool(d_fake_I, nullptr, d_fake_T, M, g_out, N, H, W, d_raw, stream);
 }
 
-extern "C" int vts_diffaug_op_ws_floats(int N) { return N * DIFFAUG_PARTS; }
+extern "C" int64_t vts_diffaug_op_ws_floats(int N) { return (int64_t)N * DIFFAUG_PARTS; }
 
 extern "C" int vts_diffaug_op(const float* x, int64_t x_ns, float* out, int64_t out_ns, int N, int C, int H, int W, int op, const float* pf,
                               const int* pi0, const int* pi1, const float* noise, const float* M, float* ws, void* stream) {

@@ -280,8 +280,8 @@ def wgrad4x4(lo0, hi0, dw, *, lo1=None, hi1=None, act_lo=0, act_hi=0, stride=2, 
         defer = lanes.defer() > 0
     ln = lanes.current(lo.device)
     prev = ln.by_dw.get(dw.data_ptr()) if defer else None
-    if prev is not None and (len(prev["segs"]) >= 4 or prev["nel"] != nel):
-        raise RuntimeError("wgrad4x4: more than 4 deferred contributions to one weight gradient")
+    if prev is not None and (len(prev["segs"]) >= L.REDUCE_MAX_SEG or prev["nel"] != nel):
+        raise RuntimeError("wgrad4x4: more than %d deferred contributions to one weight gradient" % L.REDUCE_MAX_SEG)
     ws = ln.arena.alloc(n) if defer else workspace(n, lo.device)
     d.defer = int(bool(defer))
     flops = 2.0 * d.N * d.LH * d.LW * cl * chn * 16
@@ -1063,7 +1063,7 @@ def avgpool_bwd(dy, dx, accumulate=False, channels=None, dx_nstride=None):
     return dx
 
 
-LOSS_SCALE = float(2 ** 40)     # include/vts.h VTS_LOSS_SCALE: loss slots are int64 fixed point
+LOSS_SCALE = L.LOSS_SCALE       # include/vts.h VTS_LOSS_SCALE (2^40): loss slots are int64 fixed point
 
 
 def loss_slots(n, device):
@@ -1825,7 +1825,7 @@ def spade_eval_stats(running_mean, running_var, n, eps=1e-5):
 
 
 # ---- CLIP ViT image tower (include/vts.h "CLIP ViT image tower", csrc/vts_vit.hip): skitG's style encoder, and its input-gradient backward ----
-GEMM_EPILOGUES = {"none": 0, "quickgelu": 1, "residual": 2, "quickgelu_bwd": 3}
+GEMM_EPILOGUES = {"none": L.GEMM_NONE, "quickgelu": L.GEMM_QUICKGELU, "residual": L.GEMM_RESIDUAL, "quickgelu_bwd": L.GEMM_QUICKGELU_BWD}
 
 
 def gemm_f16(a, w, bias=None, epilogue="none", out=None, out_dtype=torch.float32, aux=None):

@@ -403,6 +403,23 @@ int vts_conv4x4_flat_ok(int OH, int OW, int PH, int PW, int transposed);
 int64_t vts_conv4x4_wide_ws_floats(int N, int Cin, int Cout, int OH, int OW, int PH, int PW, int transposed);
 int vts_conv4x4_wide(const float* in, const float* wt, const float* bias, float* out, int N, int Cin, int Cout, int PH, int PW,
                      int OH, int OW, int stride, int transposed, float* ws, int64_t ws_floats, void* stream);
+/* The padding-1 transposed member of the family (the classic pix2pix U-Net, models/networks.py UnetGenerator: every up layer is
+ * ConvTranspose2d(4, 2, 1), every down layer Conv2d(4, 2, 1)):
+ *   out[n,co,y,x] = bias + sum_ci sum_{ky in 0..3 with ky = y + 1 (mod 2), kx likewise} in[n,ci,(y+1-ky)/2,(x+1-kx)/2] * wt[(ci*16 + ky*4+kx)*B + co]
+ * `in` is the input ZERO-PADDED BY ONE ON EVERY SIDE, [N,Cin,IH+2,IW+2] (vts_pad_affine, with the pending normalise + activate);
+ * out [N,Cout,2IH,2IW]; bias may be NULL.  It serves the forward of a ConvTranspose2d(4,2,1) (weight [Ci,Co,4,4] packed with A=Ci, B=Co,
+ * sa=16Co, sb=16, no flip) and the input adjoint of a Conv2d(4,2,1) (weight [Co,Ci,4,4] packed with A=Co, B=Ci, sa=16Ci, sb=16, no flip, `in`
+ * the padded output gradient).  One launch per output parity phase (2 x 2 taps each) on the family's fp32 MFMA kernels (v_mfma_f32_32x32x2_f32), split by the family's rule
+ * (vts_conv4x4_flat_ok with transposed = 1; vts_tconv4x4s2p1_flat_ok(IH, IW) tells): input maps of <= 128 pixels on the flattened-batch
+ * kernel (instance conv_flat_kernel<4, 16>, k-split through `ws`: vts_tconv4x4s2p1_wide_ws_floats), larger ones on the tiled
+ * parity-phase kernel (conv_wide_phase_kernel<4>), which needs Cout % 4 == 0 and has no k-split: measured on the MI355X it is slower
+ * than vts_conv4x4 on every U-Net shape (profiles/r24_unet_classic.md), so engine.unet_classic_* uses this entry on flat maps only.
+ * Deterministic: no float atomics.
+ * Its own adjoint and the forward of the Conv2d(4,2,1) are vts_conv4x4_wide(stride 2, transposed 0) on the operand padded by one. */
+int vts_tconv4x4s2p1_flat_ok(int IH, int IW);
+int64_t vts_tconv4x4s2p1_wide_ws_floats(int N, int Cin, int Cout, int IH, int IW);
+int vts_tconv4x4s2p1_wide(const float* in, const float* wt, const float* bias, float* out, int N, int Cin, int Cout, int IH, int IW,
+                          float* ws, int64_t ws_floats, void* stream);
 /* weight gradient of the same layers on full-size maps: dw[co][ci][ky][kx] (+)= sum dout[n,co,y,x] * in[n,ci,stride*y+ky,stride*x+kx],
  * dout [N,Cout,H,W], in [N,Cin,PH,PW] pre-padded; GEMM-class (K = pixels), deterministic slice reduction through `ws`
  * (vts_wgrad4x4_wide_ws_floats).  Small maps stay on vts_wgrad4x4. */

@@ -875,6 +875,47 @@ extern "C" int vts_conv4x4_wide(const float* in, const float* wt, const float* b
   return VTS_OK;
 }
 
+// The padding-1 transposed member of the 4 x 4 family (the classic pix2pix U-Net, reference models/networks.py UnetGenerator /
+// UnetSkipConnectionBlock: every up layer is ConvTranspose2d(4, 2, 1), every down layer Conv2d(4, 2, 1)):
+//   out[n,co,y,x] = bias + sum_{ci} sum_{ky in 0..3 with ky = y + 1 (mod 2), kx likewise} in[n,ci,(y+1-ky)/2,(x+1-kx)/2] * wt[(ci*16 + ky*4+kx)*Cout + co]
+// `in` is the input zero-padded by ONE ON EVERY SIDE, P [N,Cin,IH+2,IW+2]; out is [N,Cout,2IH,2IW].  With y = 2m + py the two live
+// tap rows are ky = 3 - py - 2a, a in {0, 1}, read at P row m + py + a: one launch per output parity phase with its 2 x 2 taps, as the
+// padding-2 member above.  The split between the two variants is the family's (vts_conv4x4_flat_ok with transposed = 1): a parity
+// phase of <= 128 pixels, i.e. an input map of <= 128 pixels, runs on the flattened-batch kernel (k-split through `ws`), larger maps
+// on the tiled parity-phase kernel.
+static bool tconv4p1_flat(int IH, int IW) { return flat_ok(IH, IW, (IH + 2) * (IW + 2), 4); }
+
+extern "C" int vts_tconv4x4s2p1_flat_ok(int IH, int IW) { return IH >= 1 && IW >= 1 && tconv4p1_flat(IH, IW) ? 1 : 0; }
+
+extern "C" int64_t vts_tconv4x4s2p1_wide_ws_floats(int N, int Cin, int Cout, int IH, int IW) {
+  if (!tconv4p1_flat(IH, IW)) return 0;
+  int ipt, cps;
+  const int KS = flat_plan(N, Cin, Cout, IH, IW, (IH + 2) * (IW + 2), 4, &ipt, &cps);
+  return KS > 1 ? (int64_t)KS * N * Cout * IH * IW : 0;
+}
+
+extern "C" int vts_tconv4x4s2p1_wide(const float* in, const float* wt, const float* bias, float* out, int N, int Cin, int Cout, int IH,
+                                     int IW, float* ws, int64_t ws_floats, void* stream) {
+  VTS_CHECK_ARG(in && wt && out && N >= 1 && Cin >= 1 && Cout >= 1 && IH >= 1 && IW >= 1, "vts_tconv4x4s2p1_wide: bad args");
+  VTS_CHECK_ARG((int64_t)N * Cout * 4 * IH * IW < (1ll << 31), "vts_tconv4x4s2p1_wide: output exceeds the 32-bit index range");
+  for (int py = 0; py < 2; ++py)
+    for (int px = 0; px < 2; ++px) {
+      WideK k{};
+      k.in = in; k.wt = wt; k.bias = bias; k.out = out; k.N = N; k.Cin = Cin; k.Cout = Cout; k.H = IH; k.W = IW;
+      k.IPH = IH + 2; k.IPW = IW + 2; k.OH = 2 * IH; k.OW = 2 * IW; k.os = 2; k.oy0 = py; k.ox0 = px;
+      k.ntaps = 0;
+      for (int a = 0; a < 2; ++a)
+        for (int b = 0; b < 2; ++b) {
+          k.dy[k.ntaps] = (signed char)(py + a); k.dx[k.ntaps] = (signed char)(px + b);
+          k.wt_tap[k.ntaps] = (signed char)((3 - py - 2 * a) * 4 + 3 - px - 2 * b);
+          ++k.ntaps;
+        }
+      const int rc = wide_launch(k, 1, ws, ws_floats, (hipStream_t)stream, 4);
+      if (rc != VTS_OK) return rc;
+    }
+  return VTS_OK;
+}
+
 // =====================================================================================================
 // Weight gradient of the same operator:
 //   dw[co][ci][ky][kx] (+)= sum_{n,y,x} dout[n,co,y,x] * in[n,ci,y+ky,x+kx]          (in pre-padded)

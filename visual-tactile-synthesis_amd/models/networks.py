@@ -151,6 +151,82 @@ class CustomUnetGenerator(nn.Module):
         return out
 
 
+class _UnetLevel(nn.Module):
+    """one UnetSkipConnectionBlock of the classic U-Net: `model` holds the reference's nn.Sequential children that own parameters,
+    registered in the reference's order (down conv, down norm, submodule, up conv, up norm), so the state dict has its keys and order"""
+
+    def __init__(self, kids):
+        super().__init__()
+        self.model = _Holder(kids)
+
+
+class UnetGenerator(nn.Module):
+    """The classic pix2pix U-Net (--netG unet_128 | unet_256; reference networks.py:1327-1426), a parameter container.
+
+    Level i (0 = outermost) owns down<i> = Conv2d(4, 2, 1): ch[i-1] -> ch[i] and up<i> = ConvTranspose2d(4, 2, 1) on
+    cat(down output of level i, up output of level i + 1): 2 ch[i] -> ch[i-1]; ch = ngf * (1, 2, 4, 8, 8, ...).  The innermost level
+    has no norm behind its down conv and no skip; the outermost none at all and Tanh behind its up conv, whose bias always exists.
+    The other conv biases exist only under InstanceNorm.  Dropout(0.5) follows the up norm of the 8 ngf -> 8 ngf middle levels
+    (4 .. num_downs - 2) when use_dropout, in train() mode.  State-dict keys are the reference's nested `model.model.1.model.3...`."""
+
+    def __init__(self, input_nc, output_nc, num_downs, ngf=64, norm="batch", use_dropout=False, opt=None):
+        super().__init__()
+        if norm not in ("instance", "batch"):
+            raise NotImplementedError("classic U-Net generator: norm %s is not built" % norm)
+        if num_downs < 5:
+            raise ValueError("UnetGenerator needs num_downs >= 5, got %d" % num_downs)
+        self.input_nc, self.output_nc, self.num_downs, self.ngf, self.norm = input_nc, output_nc, num_downs, ngf, norm
+        self.use_dropout = bool(use_dropout)
+        self.opt = opt
+        nd = num_downs
+        ch = [ngf * min(2 ** i, 8) for i in range(nd)]
+        self.channels = ch
+        bias = norm == "instance"
+
+        def bn(c):
+            return _BNParams(c) if norm == "batch" else None
+
+        downs, ups, down_norms, up_norms = [None] * nd, [None] * nd, [None] * nd, [None] * nd
+        block = None
+        for i in range(nd - 1, -1, -1):
+            cin, cout = (ch[i - 1] if i else input_nc), (ch[i - 1] if i else output_nc)
+            downs[i] = _ConvParams((ch[i], cin, 4, 4), ch[i] if bias else 0)
+            ups[i] = _ConvParams((ch[i] * (1 if i == nd - 1 else 2), cout, 4, 4), cout if (bias or i == 0) else 0, transposed=True)
+            if i == 0:          # [downconv, submodule, ReLU, upconv, Tanh]
+                kids = {0: downs[i], 1: block, 3: ups[i]}
+            elif i == nd - 1:   # [LeakyReLU, downconv, ReLU, upconv, upnorm]
+                up_norms[i] = bn(cout)
+                kids = {1: downs[i], 3: ups[i], 4: up_norms[i]}
+            else:               # [LeakyReLU, downconv, downnorm, submodule, ReLU, upconv, upnorm (, Dropout)]
+                down_norms[i], up_norms[i] = bn(ch[i]), bn(cout)
+                kids = {1: downs[i], 2: down_norms[i], 3: block, 5: ups[i], 6: up_norms[i]}
+            block = _UnetLevel({k: v for k, v in kids.items() if v is not None})
+        self.model = block
+        # flat views of the nested levels for the engine (plain tuples: the modules are registered once, under `model`)
+        self._downs, self._ups, self._down_norms, self._up_norms = tuple(downs), tuple(ups), tuple(down_norms), tuple(up_norms)
+
+    def down(self, i):
+        return self._downs[i]
+
+    def up(self, i):
+        return self._ups[i]
+
+    def down_norm(self, i):
+        return self._down_norms[i]
+
+    def up_norm(self, i):
+        return self._up_norms[i]
+
+    def dropout_levels(self):
+        """the levels whose up output passes Dropout(0.5): the num_downs - 5 middle levels of 8 ngf -> 8 ngf, outermost first"""
+        return list(range(4, self.num_downs - 1)) if self.use_dropout else []
+
+    def forward(self, x, style_code=None, verbose=False):
+        """Inference forward on the HIP path; returns [N,output_nc,H,W].  The style code is ignored, as upstream."""
+        out, _ = engine.unet_classic_forward(self, x, keep=False)
+        return out
+
+
 class _Filt(nn.Module):
     """Downsample / Upsample of the reference register their fixed blur kernel as a buffer `filt`
     (networks.py:62,99); it is part of the state_dict, so it is kept here (the HIP kernels have it built in)."""
@@ -669,9 +745,15 @@ def define_G(input_nc, output_nc, ngf, netG, norm="batch", use_dropout=False, in
                                num_upsampling_layers=getattr(opt, "num_upsampling_layers", 3), output_width=getattr(opt, "output_width", 32),
                                aspect_ratio=getattr(opt, "aspect_ratio", 1.0), use_vae=getattr(opt, "use_vae", False))
         return init_net(SPADEGenerator(input_nc, output_nc, ngf, o), init_type, init_gain, gpu_ids)
+    if netG in ("unet_128", "unet_256"):
+        # networks.py:293-296: UnetGenerator(input_nc, output_nc, 7 | 8, ngf, norm_layer, use_dropout)
+        if norm not in ("batch", "instance"):
+            raise NotImplementedError("classic U-Net generator: norm %s is not built" % norm)
+        net = UnetGenerator(input_nc, output_nc, 7 if netG == "unet_128" else 8, ngf, norm=norm, use_dropout=use_dropout, opt=opt)
+        return init_net(net, init_type, init_gain, gpu_ids)
     if netG not in resnet_blocks and netG not in ("unet256_custom", "global", "local"):
-        raise NotImplementedError("Generator model name [%s] is not recognized (built: unet256_custom, resnet_{4,6,9}blocks, global, local, "
-                                  "stylegan2, smallstylegan2, spade)" % netG)
+        raise NotImplementedError("Generator model name [%s] is not recognized (built: unet256_custom, unet_128, unet_256, "
+                                  "resnet_{4,6,9}blocks, global, local, stylegan2, smallstylegan2, spade)" % netG)
     if netG == "local":    # pix2pixHD LocalEnhancer (networks.py:311-313)
         if norm not in ("batch", "instance"):
             raise NotImplementedError("local enhancer: norm %s is not built" % norm)

@@ -633,6 +633,14 @@ class SinSKITGModel(GraphedStepModel):
                 raise NotImplementedError("style codes are only built for netG=unet256_custom")
             g_out, self._g_ctx = engine.resnet_forward(self.netG, self._g_input(), keep=keep,
                                                        dropout_masks=self._draws.get("dropout") if self._draws is not None else None)
+        elif isinstance(self.netG, networks.UnetGenerator):
+            # the classic pix2pix U-Net (--netG unet_128 | unet_256): forward(input, style_code=None) ignores the style code upstream
+            # (networks.py:1354-1356); said once here
+            if self._style() is not None and not getattr(self, "_style_ignored_said", False):
+                self._style_ignored_said = True
+                print("--netG %s ignores the style code (as upstream: UnetGenerator.forward drops it)" % opt.netG, flush=True)
+            g_out, self._g_ctx = engine.unet_classic_forward(self.netG, self._g_input(), keep=keep,
+                                                             dropout_masks=self._draws.get("dropout") if self._draws is not None else None)
         elif not keep:
             # inference: one call of the network-level C entry (include/vts.h: vts_unet_forward) where it covers the configuration
             g_out, self._g_ctx = engine.unet_forward_infer(self.netG, self._g_input(), style_code=self._style(),
@@ -1109,6 +1117,8 @@ class SinSKITGModel(GraphedStepModel):
                        coarse=gp.get("coarse_grad") if gp is not None else None)
         if isinstance(self.netG, networks.ResnetGenerator):
             engine.resnet_backward(self.netG, self._g_ctx, d_raw)
+        elif isinstance(self.netG, networks.UnetGenerator):
+            engine.unet_classic_backward(self.netG, self._g_ctx, d_raw)
         elif part == "decoder":
             self._g_bwd_state = engine.unet_backward_decoder(self.netG, self._g_ctx, d_raw)
         else:

@@ -594,6 +594,244 @@ def _unet_backward_encoder(G, ctx, dfeat, feats, nd, dev, sq):
 
 
 # -------------------------------------------------------------------------------------
+# classic pix2pix U-Net (--netG unet_128 | unet_256): reference models/networks.py:1327-1426
+# -------------------------------------------------------------------------------------
+# Level i (0 = outermost): feats[i] = [norm](down<i>(LeakyReLU(feats[i-1]))), u[i] = [norm](up<i>(ReLU(cat[feats[i], u[i+1]]))).  The
+# reference's in-place LeakyReLU rewrites the skip before the cat, but every consumer of a cat starts with ReLU and
+# ReLU(LeakyReLU(x)) = ReLU(x): the skip is ReLU(raw feature) in the forward and in the gradient.
+#
+# A launch whose OUTPUT has at most 80 channels runs on the 4 x 4 kernels (vts_conv4x4: operands on load), as every layer of the
+# model's default ngf = 10 does.  Above that the 4 x 4 kernels would loop over 80-channel groups that each re-read the input; those
+# launches take the GEMM-class family on operands pre-padded by one (vts_pad_affine: one call per concat source into its channel slice,
+# with the pending norm and activation):
+#   down forward, up input adjoint      vts_conv4x4_wide(stride 2)
+#   up forward, down input adjoint      vts_tconv4x4s2p1_wide on input maps of <= 128 pixels (its flattened-batch kernel, k-split; see
+#                                       _uc_tconv_wide for the one band of batch sizes left out).  On larger maps its tiled parity-phase
+#                                       kernel (four launches, no k-split) measured 1.3 - 7x SLOWER than the group loop on every shape
+#                                       of unet_256 at ngf 64 (profiles/r24_unet_classic.md): those launches STAY on vts_conv4x4, group
+#                                       loop included -- with the band, 10 of the 12 such launches of unet_256 at ngf 64 and 1024 x 1024, batch 1
+# with the derivative mask of the consumer applied behind the adjoint (vts_act_bwd), as in the wide PatchGAN backward.
+
+UC_WIDE_MIN_CO = 81
+UC_TRACE = None      # a list: every convolution launch of the classic U-Net appends (layer, role, output channels, vts_last_kernel)
+
+
+def _uc_wide(cout):
+    """more than 80 output channels, in 16-byte packed weight rows (a count that is no multiple of 4, ngf 41's 82, stays on vts_conv4x4)"""
+    return cout >= UC_WIDE_MIN_CO and cout % 4 == 0
+
+
+def _uc_tconv_wide(cout, n, ih, iw):
+    """the padding-1 transposed member serves this launch: more than 80 output channels on an input map its flattened-batch kernel takes
+    (<= 128 pixels), unless the flattened batch fills between a quarter and all of one 128-pixel tile (32 < n ih iw < 128): there half the
+    MFMA columns are empty under the deepest k-split, and the entry measured 8 - 27 % slower than vts_conv4x4 on all four such shapes of
+    unet_256 at ngf 64, against 0.51 - 0.94 of its time at 128 pixels and more and 0.81 - 1.03 at 32 and fewer (profiles/r24_unet_classic.md)"""
+    return _uc_wide(cout) and not (32 < n * ih * iw < 128) and ops.tconv4x4s2p1_flat_ok(ih, iw)
+
+
+def _uc_note(layer, role, cout):
+    if UC_TRACE is not None:
+        UC_TRACE.append((layer, role, cout, L.load().vts_last_kernel().decode()))
+
+
+def _uc_padded(srcs, act):
+    """act(norm(cat(srcs))) zero-padded by one as one identity tensor: each source is written into its channel slice"""
+    srcs = [s for s in srcs if s is not None]
+    n, _, h, w = srcs[0].data.shape
+    buf = torch.empty(n, sum(s.data.shape[1] for s in srcs), h + 2, w + 2, dtype=torch.float32, device=srcs[0].data.device)
+    c0 = 0
+    for s in srcs:
+        c = s.data.shape[1]
+        ops.pad_affine(s, (1, 1, 1, 1), 0, out=buf[:, c0:c0 + c], act=act, out_nstride=buf.stride(0))
+        c0 += c
+    return buf
+
+
+def _uc_bn_kw(bn):
+    return dict(gamma=bn.weight, beta=bn.bias, running_mean=bn.running_mean, running_var=bn.running_var, nbt=bn.num_batches_tracked)
+
+
+class UnetClassicCtx:
+    __slots__ = ("x", "feats", "ups", "below", "drops", "padded", "g_out")
+
+
+def unet_classic_forward(G, x, keep=True, dropout_masks=None):
+    """x: [N, input_nc, H, W] tensor / Act, or a pair (x0, x1) concatenated on load (sketch ++ positional grid).
+    Returns (g_out [N, output_nc, H, W] post-tanh, ctx).  train() mode: BatchNorm uses the batch statistics and advances the running
+    ones, Dropout is live; eval(): the running statistics, no Dropout.
+    dropout_masks: {level: keep mask [N, C, h, w] of 0 / 1} for G.dropout_levels() (drawn with torch.bernoulli when absent)"""
+    if isinstance(x, (tuple, list)):
+        x, x_extra = _as_act(x[0]), _as_act(x[1])
+    else:
+        x, x_extra = _as_act(x), None
+    n, _, h, w = x.data.shape
+    dev = x.data.device
+    nd, ch = G.num_downs, G.channels
+    if h % (1 << nd) or w % (1 << nd):
+        raise ValueError("unet_%d needs H, W divisible by %d, got %dx%d" % (1 << nd, 1 << nd, h, w))
+    feats, padded = [], {}
+    a = x
+    for i in range(nd):
+        conv, bn = G.down(i), G.down_norm(i)
+        normed = 0 < i < nd - 1
+        out = _empty(n, ch[i], h >> (i + 1), w >> (i + 1), dev)
+        act_in = LRELU if i else 0
+        if _uc_wide(ch[i]):
+            p = padded[i] = _uc_padded((a, x_extra if i == 0 else None), act_in)
+            ops.conv4x4_wide(p, ops.w4x4_pack(conv.weight, "conv_fwd"), conv.bias, out, stride=2)
+            _uc_note("down%d" % i, "forward", ch[i])
+            r = _g_norm(G, out, bn) if normed else Act(out)
+        else:
+            cin = conv.weight.shape[1]
+            fused = normed and (bn is None or G.training)
+            kw = {} if not fused else (dict(instance_norm=True) if bn is None else dict(batch_norm=_uc_bn_kw(bn)))
+            r = ops.conv4x4(a, conv.weight, cin * 16, 16, ch[i], out, in1=x_extra if i == 0 else None, bias=conv.bias, stride=2, pad=1,
+                            act_in=act_in, **kw)
+            _uc_note("down%d" % i, "forward", ch[i])
+            if not fused:
+                r = _g_norm(G, out, bn) if normed else Act(out)
+        feats.append(r)
+        a = r
+
+    g_out = _empty(n, G.output_nc, h, w, dev)
+    drop_levels = G.dropout_levels() if G.training else []
+    ups, below, drops = [None] * nd, [None] * nd, {}
+    u = None
+    for i in range(nd - 1, -1, -1):
+        conv, bn = G.up(i), G.up_norm(i)
+        below[i] = u
+        outer = conv.weight.shape[1]
+        hh, ww = h >> (i + 1), w >> (i + 1)
+        out = g_out if i == 0 else _empty(n, outer, 2 * hh, 2 * ww, dev)
+        normed = i != 0
+        if _uc_tconv_wide(outer, n, hh, ww):
+            p = _uc_padded((feats[i], u), RELU)
+            ops.tconv4x4s2p1_wide(p, ops.w4x4_pack(conv.weight, "convT_fwd"), conv.bias, out)
+            _uc_note("up%d" % i, "forward", outer)
+            r = _g_norm(G, out, bn)      # (the outermost layer has output_nc channels: never here)
+        else:
+            fused = normed and (bn is None or G.training)
+            kw = {} if not fused else (dict(instance_norm=True) if bn is None else dict(batch_norm=_uc_bn_kw(bn)))
+            r = ops.conv4x4(feats[i], conv.weight, 16, outer * 16, outer, out, in1=u, bias=conv.bias, stride=2, pad=1, transposed=True,
+                            act_in=RELU, act_out=TANH if i == 0 else 0, **kw)
+            _uc_note("up%d" % i, "forward", outer)
+            if not fused:
+                r = _g_norm(G, out, bn) if normed else Act(out)
+        ups[i] = r
+        if i in drop_levels:
+            # Dropout(0.5) behind the norm: the normalised map is materialised and multiplied by keep * 2 (small maps: 8 ngf channels at
+            # <= 1/16 of the resolution); the level above reads it as a plain tensor, the backward multiplies by the same map
+            keep2 = dropout_masks.get(i) if dropout_masks is not None else None
+            if keep2 is None:
+                keep2 = torch.bernoulli(torch.full(out.shape, 0.5, device=dev))
+            keep2 = (keep2.to(device=dev, dtype=torch.float32) * 2.0).contiguous()
+            y = ops.pad_affine(r, (0, 0, 0, 0), 0)
+            yd = torch.empty_like(y)
+            ops.mask_mul(y.view(-1, 1, y.shape[2], y.shape[3]), keep2.view(-1, 1, y.shape[2], y.shape[3]), out=yd.view(-1, 1, y.shape[2], y.shape[3]))
+            drops[i] = keep2
+            r = Act(yd)
+        u = r
+    if not keep:
+        return g_out, None
+    ctx = UnetClassicCtx()
+    ctx.x, ctx.feats, ctx.ups, ctx.below, ctx.drops, ctx.padded, ctx.g_out = (x, x_extra), feats, ups, below, drops, padded, g_out
+    return g_out, ctx
+
+
+def unet_classic_backward(G, ctx, d_raw):
+    """d_raw: [N, output_nc, H, W] gradient w.r.t. the pre-tanh output.  Writes every parameter's .grad (overwrite; allocated where
+    missing).  A conv bias that feeds a normalisation has an identically zero gradient: its .grad is zeroed, not computed.  Weight-gradient
+    partials are reduced deterministically, in a fixed order, by one launch at the end (ops.deferred_wgrad).  No gradient w.r.t. the
+    network input is formed."""
+    if not G.training and G.norm == "batch":
+        raise RuntimeError("unet_classic_backward: BatchNorm backward needs the batch statistics of a train() forward")
+    nd, ch = G.num_downs, G.channels
+    dev = d_raw.device
+    feats = ctx.feats
+    for p in G.parameters():
+        if p.grad is None:
+            p.grad = torch.zeros_like(p)
+
+    def norm_bwd(g, a, bn):
+        if bn is None:
+            ops.norm_bwd(g, a, 0)
+        else:
+            ops.norm_bwd(g, a, 1, gamma=bn.weight, dgamma=bn.weight.grad, dbeta=bn.bias.grad)
+
+    with ops.deferred_wgrad():
+        dfeat = [None] * nd
+        g = d_raw
+        for i in range(nd):
+            conv, bn = G.up(i), G.up_norm(i)
+            outer = conv.weight.shape[1]
+            if i:
+                if i in ctx.drops:      # Dropout backward: the same keep * 2 map
+                    gd = torch.empty_like(g)
+                    ops.mask_mul(g.view(-1, 1, g.shape[2], g.shape[3]), ctx.drops[i].view(-1, 1, g.shape[2], g.shape[3]), out=gd.view(-1, 1, g.shape[2], g.shape[3]))
+                    g = gd
+                norm_bwd(g, ctx.ups[i], bn)
+            gop = Act(g)
+            skip, below = feats[i], ctx.below[i]      # the concat sources up<i> consumed (below: the level below's output, behind its Dropout)
+            # (vts_wgrad4x4_wide with the roles swapped -- the activated input as dout, the padded gradient as p, both materialised --
+            #  measured slower than this on 7 of the 8 full-size up layers of unet_256 at ngf 64: profiles/r24_unet_classic.md)
+            ops.wgrad4x4(skip, gop, conv.weight.grad, lo1=below, act_lo=RELU, stride=2, pad=1)
+            if i == 0:
+                ops.channel_sum(g, conv.bias.grad)
+            elif conv.bias is not None:
+                conv.bias.grad.zero_()
+            c = ch[i]
+            srcs = [(skip, 0)] + ([(below, c)] if below is not None else [])
+            q = ops.pad_affine(g, (1, 1, 1, 1), 0) if _uc_wide(c) else None
+            g_next = None
+            for src, c0 in srcs:
+                if src is skip:
+                    tgt, acc = add_grad_list(dfeat, i, src.data.shape, dev)
+                else:
+                    tgt, acc = torch.empty_like(src.data), False
+                    g_next = tgt
+                wv = conv.weight[c0:c0 + c]      # this source's rows of the [Cin, Cout, 4, 4] weight: contiguous
+                if q is not None:
+                    raw = torch.empty_like(src.data)
+                    ops.conv4x4_wide(q, ops.w4x4_pack(wv, "convT_adj"), None, raw, stride=2)
+                    _uc_note("up%d" % i, "adjoint", c)
+                    ops.act_bwd(raw, src, RELU, tgt, accumulate=acc)
+                else:
+                    ops.conv4x4(gop, wv, outer * 16, 16, c, tgt, stride=2, pad=1, dmask=src, dmask_act=RELU, accumulate=acc)
+                    _uc_note("up%d" % i, "adjoint", c)
+            g = g_next
+        for i in range(nd - 1, -1, -1):
+            conv, bn = G.down(i), G.down_norm(i)
+            g = dfeat[i]
+            if 0 < i < nd - 1:
+                norm_bwd(g, feats[i], bn)
+            src, src1 = ctx.x if i == 0 else (feats[i - 1], None)
+            p = ctx.padded.get(i)
+            if p is not None and not ops.conv4x4_flat_ok(g.shape[2], g.shape[3], p.shape[2], p.shape[3]):
+                ops.wgrad4x4_wide(g, p, conv.weight.grad, stride=2)      # full-size map: GEMM-class
+            else:
+                ops.wgrad4x4(Act(g), src, conv.weight.grad, hi1=src1, act_hi=LRELU if i else 0, stride=2, pad=1)
+            if conv.bias is not None:
+                if 0 < i < nd - 1:
+                    conv.bias.grad.zero_()
+                else:
+                    ops.channel_sum(g, conv.bias.grad)
+            if i > 0:
+                cin = conv.weight.shape[1]
+                prev = feats[i - 1]
+                tgt, acc = add_grad_list(dfeat, i - 1, prev.data.shape, dev)
+                if _uc_tconv_wide(cin, g.shape[0], g.shape[2], g.shape[3]):
+                    raw = torch.empty_like(prev.data)
+                    ops.tconv4x4s2p1_wide(ops.pad_affine(g, (1, 1, 1, 1), 0), ops.w4x4_pack(conv.weight, "conv_s2_adj"), None, raw)
+                    _uc_note("down%d" % i, "adjoint", cin)
+                    ops.act_bwd(raw, prev, LRELU, tgt, accumulate=acc)
+                else:
+                    ops.conv4x4(Act(g), conv.weight, 16, cin * 16, cin, tgt, stride=2, pad=1, transposed=True, dmask=prev, dmask_act=LRELU,
+                                accumulate=acc)
+                    _uc_note("down%d" % i, "adjoint", cin)
+            dfeat[i] = None
+
+
+# -------------------------------------------------------------------------------------
 # ResNet generator (--netG resnet_{4,6,9}blocks): /root/reference/models/networks.py:1051-1154
 # -------------------------------------------------------------------------------------
 

@@ -821,6 +821,9 @@ def wgrad3x3_wide(dout, p, dw, accumulate=False, stride=1):
 def w4x4_pack(w, mode, tag=None):
     """tap-major packing of an nn.Conv2d weight [Co,Ci,4,4] for conv4x4_flat (see include/vts.h) into a persistent buffer"""
     d0, d1 = w.shape[0], w.shape[1]
+    # (convT_fwd / convT_adj are ALIASES of conv_s2_adj / conv_fwd, named for an nn.ConvTranspose2d weight [Ci,Co,4,4] of stride 2: its
+    #  forward packs like the stride-2 adjoint of a Conv2d weight, its input adjoint like a Conv2d forward; an alias shares the buffer)
+    mode = {"convT_fwd": "conv_s2_adj", "convT_adj": "conv_fwd"}.get(mode, mode)
     A, B, sa, sb, flip = {"conv_fwd": (d1, d0, 16, 16 * d1, 0), "conv_adj": (d0, d1, 16 * d1, 16, 1),
                           "conv_s2_adj": (d0, d1, 16 * d1, 16, 0)}[mode]
     key = ("wt4", w.data_ptr(), tuple(w.shape), mode, tag)
@@ -851,6 +854,31 @@ def conv4x4_wide(p, wt, bias, out, stride=1, transposed=False):
     _run("conv3x3_wide", 4.0 * (p.numel() + out.numel() + wt.numel()), 2.0 * n * oh * ow * co * ci * taps, lib.vts_conv4x4_wide,
          p.data_ptr(), wt.data_ptr(), L.ptr(bias), out.data_ptr(), n, ci, co, ph, pw, oh, ow, stride, int(transposed), L.ptr(ws),
          ws.numel() if ws is not None else 0, L.stream())
+    return out
+
+
+def tconv4x4s2p1_flat_ok(ih, iw):
+    """whether tconv4x4s2p1_wide runs an ih x iw input map on its flattened-batch kernel (<= 128 pixels)"""
+    return bool(L.load().vts_tconv4x4s2p1_flat_ok(ih, iw))
+
+
+def tconv4x4s2p1_wide(p, wt, bias, out):
+    """out [N,Co,2IH,2IW] <- ConvTranspose2d(4, stride 2, pad 1) of p [N,Ci,IH+2,IW+2] (the input zero-padded by one) with 16-tap packed
+    weights (w4x4_pack convT_fwd); with conv_s2_adj packing and p the padded output gradient: the input adjoint of Conv2d(4, 2, 1)"""
+    n, ci, ph, pw = p.shape
+    co = out.shape[1]
+    ih, iw = ph - 2, pw - 2
+    assert out.shape == (n, co, 2 * ih, 2 * iw) and p.is_contiguous() and out.is_contiguous()
+    assert wt.numel() == ci * 16 * ((co + 3) // 4 * 4)
+    lib = L.load()
+    need = lib.vts_tconv4x4s2p1_wide_ws_floats(n, ci, co, ih, iw)
+    ws = workspace(need, p.device) if need else None
+    if TIMER is not None:
+        global DETAIL
+        DETAIL = "N%d %dx%dx%d -> %dx%dx%d transposed s2 p1" % (n, ci, ih, iw, co, 2 * ih, 2 * iw)
+    _run("conv3x3_wide", 4.0 * (p.numel() + out.numel() + wt.numel()), 2.0 * n * 4 * ih * iw * co * ci * 4, lib.vts_tconv4x4s2p1_wide,
+         p.data_ptr(), wt.data_ptr(), L.ptr(bias), out.data_ptr(), n, ci, co, ih, iw, L.ptr(ws), ws.numel() if ws is not None else 0,
+         L.stream())
     return out
 
 

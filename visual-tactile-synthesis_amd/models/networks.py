@@ -261,50 +261,25 @@ class ResnetGenerator(nn.Module):
         self._block_keys = ("1", "2", str(kb), str(kb + 1))
         if conv_bias is None:          # ResnetGenerator: use_bias = (norm_layer == InstanceNorm2d)  (networks.py:1069-1073)
             conv_bias = norm == "instance"
-        mods, layout = {}, []
-        idx = 0
-
-        def add(kind, mod=None, **kw):
-            nonlocal idx
-            if mod is not None:
-                mods[idx] = mod
-            layout.append(dict(kind=kind, idx=idx, **kw))
-            idx += 1
-
-        def add_norm(c):
-            add("norm", _BNParams(c) if norm == "batch" else None)
-
-        def block(c):
-            kids = {1: _ConvParams((c, c, 3, 3), c if conv_bias else 0), kb: _ConvParams((c, c, 3, 3), c if conv_bias else 0)}
-            if norm == "batch":
-                kids[2], kids[kb + 1] = _BNParams(c), _BNParams(c)
-            return _Holder({"conv_block": _Holder(dict(sorted(kids.items())))})     # (state-dict order as upstream: conv, norm, conv, norm)
-
-        add("pad")
-        add("conv7", _ConvParams((ngf, input_nc, 7, 7), ngf if conv_bias else 0))
-        add_norm(ngf); add("relu")
+        b = _SeqBuilder(norm, conv_bias, block_second=kb, block_sorted=True)
+        b.conv7(input_nc, ngf)
         for i in range(n_downsampling):
             c = ngf * 2 ** i
-            add("conv3", _ConvParams((2 * c, c, 3, 3), 2 * c if conv_bias else 0), stride=2 if down == "stride" else 1)
-            add_norm(2 * c); add("relu")
+            b.conv3(c, 2 * c, 2 if down == "stride" else 1)
             if down == "blur":
-                add("down", _Filt(2 * c, [1.0, 2.0, 1.0], 1.0))
-        c = ngf * 2 ** n_downsampling
+                b.add("down", _Filt(2 * c, [1.0, 2.0, 1.0], 1.0))
         for _ in range(n_blocks):
-            add("block", block(c))
+            b.block(ngf * 2 ** n_downsampling)
         for i in range(n_downsampling):
             c = ngf * 2 ** (n_downsampling - i)
             if up == "blur":
-                add("up", _Filt(c, [1.0, 3.0, 3.0, 1.0], 4.0))
-                add("conv3", _ConvParams((c // 2, c, 3, 3), c // 2 if conv_bias else 0), stride=1)
+                b.add("up", _Filt(c, [1.0, 3.0, 3.0, 1.0], 4.0))
+                b.conv3(c, c // 2, 1)
             else:
-                add("convT3", _ConvParams((c, c // 2, 3, 3), c // 2 if conv_bias else 0, transposed=True))
-            add_norm(c // 2); add("relu")
-        add("pad")
-        add("conv7", _ConvParams((output_nc, ngf, 7, 7), output_nc))
-        add("tanh")
-        self.model = _Holder(mods)
-        self.layout = layout
+                b.convT3(c, c // 2)
+        b.conv7(ngf, output_nc, final=True)
+        self.model = _Holder(b.mods)
+        self.layout = b.layout
 
     def mod(self, idx):
         return getattr(self.model, str(idx), None)
@@ -320,10 +295,14 @@ class ResnetGenerator(nn.Module):
 
 
 class _SeqBuilder:
-    """collects (module index -> parameter container) and the layout list of one nn.Sequential of the reference"""
+    """collects (module index -> parameter container) and the layout list of one nn.Sequential of the reference.
+    block_second: the key of a block's second convolution inside conv_block (5; 6 behind a Dropout).  block_sorted: a block registers
+    conv, norm, conv, norm as upstream does (ResnetGenerator); the LocalEnhancer's containers have always registered conv, conv, norm, norm,
+    and the order of a state dict is the order of the flat parameter buffer, so each keeps its own."""
 
-    def __init__(self, norm, conv_bias=True):
+    def __init__(self, norm, conv_bias=True, block_second=5, block_sorted=False):
         self.mods, self.layout, self.idx, self.norm, self.conv_bias = {}, [], 0, norm, conv_bias
+        self.block_second, self.block_sorted = block_second, block_sorted
 
     def add(self, kind, mod=None, **kw):
         if mod is not None:
@@ -352,14 +331,15 @@ class _SeqBuilder:
         self.norm_relu(cout)
 
     def block(self, c):
-        kids = {1: _ConvParams((c, c, 3, 3), c if self.conv_bias else 0), 5: _ConvParams((c, c, 3, 3), c if self.conv_bias else 0)}
+        kb = self.block_second
+        kids = {1: _ConvParams((c, c, 3, 3), c if self.conv_bias else 0), kb: _ConvParams((c, c, 3, 3), c if self.conv_bias else 0)}
         if self.norm == "batch":
-            kids[2], kids[6] = _BNParams(c), _BNParams(c)
-        self.add("block", _Holder({"conv_block": _Holder(kids)}))
+            kids[2], kids[kb + 1] = _BNParams(c), _BNParams(c)
+        self.add("block", _Holder({"conv_block": _Holder(dict(sorted(kids.items())) if self.block_sorted else kids)}))
 
 
 class _SeqView:
-    """layout + module lookup over one _Holder (what engine._seq_forward walks); not an nn.Module"""
+    """layout + module lookup over one _Holder (what engine._seq_units groups and engine._seq_forward runs); not an nn.Module"""
 
     def __init__(self, holder, layout):
         self._holder, self.layout = holder, layout

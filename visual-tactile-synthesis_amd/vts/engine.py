@@ -1,17 +1,15 @@
-"""Explicit forward / backward schedules of the two network families over libvts_hip.so.
+"""Explicit forward / backward schedules of every network over libvts_hip.so.
 
-There is no autograd on the hot path: the U-Net generator and the multiscale PatchGAN
-discriminator are fixed graphs, so their backward passes are written out as kernel
-sequences.  Activations travel as `ops.Act` (raw tensor + per-(n,c) scale/shift): a
-normalisation layer is a statistics pass only, and every consumer (next conv, skip
-concat, derivative mask, weight gradient) normalises on load inside the conv kernels.
+There is no autograd on the hot path: the networks are fixed graphs, so their backward passes are written out as kernel sequences (PyTorch
+autograd in the reference).  Activations travel as `ops.Act` (raw tensor + per-(n,c) scale/shift): a normalisation layer is a statistics
+pass only, and every consumer (next conv, skip concat, derivative mask, weight gradient) normalises on load inside the conv kernels.
 
-Reference graphs reproduced here:
-  CustomUnetGenerator.forward     /root/reference/models/networks.py:1576-1645
-  Down / Up blocks                /root/reference/thirdparty/unet/unet_parts_custom.py:9-79
-  MultiscaleDiscriminator.forward /root/reference/models/networks.py:1682-1693
-  NLayerDiscriminator             /root/reference/models/networks.py:1696-1750
-(their backward is PyTorch autograd in the reference).
+In file order, each section under a banner that cites the reference graph it reproduces:
+  style-conditioned U-Net (unet_*; CustomUnetGenerator), the classic pix2pix U-Net (unet_classic_*)
+  the ResNet family (resnet_*, local_enhancer_forward: ResnetGenerator, pix2pixHD GlobalGenerator / LocalEnhancer), one record per layer
+  the multiscale PatchGAN discriminators (msd_*), SideQueue and the lane helpers the step schedules fork with
+  StyleGAN2 discriminator, generator and modulated convolutions (sg2d_*, sg2g_*, modulated_conv2d ...)
+  SIFID / T_FID evaluation metrics, and the SPADE generator (spade_*)
 """
 import ctypes as C
 import os
@@ -832,11 +830,14 @@ def unet_classic_backward(G, ctx, d_raw):
 
 
 # -------------------------------------------------------------------------------------
-# ResNet generator (--netG resnet_{4,6,9}blocks): /root/reference/models/networks.py:1051-1154
+# ResNet family (--netG resnet_{4,6,9}blocks, pix2pixHD global / local): reference models/networks.py:1051-1154, 1897-1980
 # -------------------------------------------------------------------------------------
 
 class ResnetCtx:
     __slots__ = ("steps", "g_out")
+
+    def __init__(self, steps, g_out):
+        self.steps, self.g_out = steps, g_out
 
 
 def _g_norm(G, r, bn):
@@ -860,169 +861,330 @@ def _g_norm_bwd(buf, a, bn):
         ops.norm_bwd(buf, a, 1, gamma=bn.weight, dgamma=bn.weight.grad, dbeta=bn.bias.grad)
 
 
-def _is_wide(conv):
-    """layers big enough for the GEMM-class 3x3 kernel (vts_conv3x3_wide) to pay: >= 64 x 64 channels"""
+def _through_norm_relu(g_act, a, bn):
+    """gradient w.r.t. relu(norm(r)) -> gradient w.r.t. the raw conv output r (in a fresh buffer)"""
+    buf = torch.empty_like(a.data)
+    ops.act_bwd(g_act, a, RELU, buf)
+    _g_norm_bwd(buf, a, bn)
+    return buf
+
+
+def _into_producer(d, inp, inp_act, bn_of):
+    """gradient w.r.t. a layer's input as loaded -> w.r.t. what the layer below produced: through relu(norm(.)) where a ReLU was pending (bn_of: _bn_map)"""
+    return _through_norm_relu(d, inp, bn_of.get(id(inp))) if inp_act == RELU else d
+
+
+def _mask_mul(x, keep2):
+    """x * keep2 in a fresh buffer (Dropout and its backward: the same keep * 2 map)"""
+    v = lambda t: t.view(-1, 1, t.shape[2], t.shape[3])
+    return ops.mask_mul(v(x), v(keep2)).view(x.shape)
+
+
+class _Flow:
+    """what a segment's forward threads through its layers: cur, the activation (an Act whose `pending` activation the consumer applies on load, or an
+    identity tensor; None in front of the network input, whose `srcs` are concatenated on store), G for the train / eval mode, the unused Dropout masks"""
+    __slots__ = ("G", "cur", "pending", "srcs", "masks")
+
+
+class _Step:
+    """One record per layer of a segment, next to its pair: _<kind>_forward(f, e, *modules) takes the _Flow and the layout entry, returns the record;
+    _<kind>_backward(st, g, sq, bn_of) takes the gradient w.r.t. the layer's output (the raw conv output where the kind ends in a norm), writes the
+    parameters' .grad through the side queue and returns the gradient w.r.t. what the layer below produced.  `wide` / `wino`: the kernel routes the
+    forward chose; the backward reads them."""
+    __slots__ = ()
+    out = bn = None     # kinds that end in a norm: the normalised output (Act) and its BatchNorm module (None: InstanceNorm)
+
+    def weights(self):      # the convolution weights this step owns
+        return [self.conv.weight] if hasattr(self, "conv") else []
+
+
+def _pad3_conv7(conv, f):
+    """ReflectionPad2d(3) + 7x7 convolution (4x4 tap blocks) -> (padded operand, the Act it was padded from | None, raw output)"""
+    if f.cur is None:    # network input: concat the sources while padding
+        n, _, h, w = f.srcs[0].data.shape
+        p = _empty(n, sum(s.data.shape[1] for s in f.srcs), h + 6, w + 6, f.srcs[0].data.device)
+        c0 = 0
+        for s in f.srcs:
+            c = s.data.shape[1]
+            ops.pad_affine(s, (3, 3, 3, 3), 1, out=p[:, c0:c0 + c], out_nstride=p.stride(0))
+            c0 += c
+        src = None
+    else:
+        p = ops.pad_affine(f.cur, (3, 3, 3, 3), 1, act=f.pending)
+        src = f.cur if isinstance(f.cur, Act) else None
+    r = _empty(p.shape[0], conv.weight.shape[0], p.shape[2] - 6, p.shape[3] - 6, p.device)
+    ops.convk(p, conv.weight, r, bias=conv.bias, pad=0)
+    return p, src, r
+
+
+class Conv7Ctx(_Step):
+    """ReflectionPad2d(3) + Conv2d(7) + norm + relu (the ReLU rides on `out` as the pending activation)"""
+    __slots__ = ("conv", "p", "src", "out", "bn")
+
+
+def _conv7_forward(f, e, conv, bn):
+    st = Conv7Ctx()
+    st.conv, st.bn = conv, bn
+    st.p, st.src, r = _pad3_conv7(conv, f)
+    st.out = f.cur = _g_norm(f.G, r, bn)
+    f.pending = RELU
+    return st
+
+
+def _conv7_backward(st, g, sq, bn_of):
+    sq.run(lambda: ops.wgradk(g, st.p, st.conv.weight.grad, pad=0), g)  # network input: no gradient needed below
+    return g
+
+
+class Conv7OutCtx(_Step):
+    """the final ReflectionPad2d(3) + Conv2d(7) + tanh; src: the Act relu(norm(r_prev)) the operand p was padded from"""
+    __slots__ = ("conv", "p", "src")
+
+
+def _conv7_out_forward(f, e, conv, _):
+    st = Conv7OutCtx()
+    st.conv = conv
+    st.p, st.src, r = _pad3_conv7(conv, f)
+    f.cur = ops.pad_affine(r, (0, 0, 0, 0), 0, act=TANH)
+    return st
+
+
+def _conv7_out_backward(st, g, sq, bn_of):
+    conv, p = st.conv, st.p
+    sq.run(lambda: (ops.wgradk(g, p, conv.weight.grad, pad=0), ops.channel_sum(g, conv.bias.grad)), g)
+    dp = ops.convk_bwd_data(g, conv.weight, torch.empty_like(p), pad=0)
+    da = ops.pad_bwd(dp, (3, 3, 3, 3), 1, _empty(p.shape[0], p.shape[1], p.shape[2] - 6, p.shape[3] - 6, g.device))
+    return _through_norm_relu(da, st.src, bn_of.get(id(st.src)))
+
+
+class Conv3Ctx(_Step):
+    """Conv2d(3, pad 1, stride 1 | 2) + norm + relu.  wide: on the GEMM-class kernels, whose operand xp = act(inp) was materialised with
+    its zero padding once; else on the 4x4 family, which applies inp_act on load"""
+    __slots__ = ("conv", "inp", "inp_act", "out", "bn", "stride", "wide", "xp")
+
+
+def _conv3_forward(f, e, conv, bn):
+    st = Conv3Ctx()
+    st.conv, st.bn, st.inp, st.inp_act, st.stride, st.xp = conv, bn, f.cur, f.pending, e["stride"], None
+    stride, x = st.stride, _as_act(f.cur).data
+    n, _, ih, iw = x.shape
     co, ci = conv.weight.shape[:2]
-    return co >= 64 and ci >= 64 and co % 4 == 0 and ci % 4 == 0 and conv.weight.shape[2] == 3
+    r = _empty(n, co, (ih - 1) // stride + 1, (iw - 1) // stride + 1, x.device)
+    if stride == 2 and (ih % 2 or iw % 2):
+        raise ValueError("stride-2 3x3 convolutions need even sizes, got %dx%d" % (ih, iw))
+    st.wide = ops.conv3_wide(conv.weight)
+    if st.wide:
+        st.xp = ops.pad_affine(st.inp, (1, 1, 1, 1), 0, act=st.inp_act)
+        wt = ops.w3x3_pack(conv.weight, "conv_fwd")
+        (ops.conv3x3_wide if stride == 1 else ops.conv3x3s2_wide)(st.xp, wt, conv.bias, r)
+    elif stride == 1:
+        ops.convk(st.inp, conv.weight, r, bias=conv.bias, pad=1, act_in=st.inp_act)
+    else:
+        ops.conv4x4(st.inp, ops.tap_embed3(conv.weight), ci * 16, 16, co, r, bias=conv.bias, stride=2, pad=1, act_in=st.inp_act)
+    st.out = f.cur = _g_norm(f.G, r, bn)
+    f.pending = RELU
+    return st
 
 
-def _conv_valid3(p, conv, out):
-    """valid 3x3 conv of a pre-padded identity tensor"""
-    if _is_wide(conv):
-        n, ci, ph, pw = p.shape
-        if ops.conv3x3_wino_ok(n, ci, out.shape[1], ph - 2, pw - 2):      # Winograd F(2x2, 3x3): 1.5 - 1.9x the direct kernel (round 4)
-            return ops.conv3x3_wino(p, ops.w3x3_wino_pack(conv.weight, "conv_fwd"), conv.bias, out)
-        return ops.conv3x3_wide(p, ops.w3x3_pack(conv.weight, "conv_fwd"), conv.bias, out)
-    return ops.convk(p, conv.weight, out, bias=conv.bias, pad=0)
+def _conv3_backward(st, g, sq, bn_of):
+    conv, inp, inp_act, stride, xp = st.conv, st.inp, st.inp_act, st.stride, st.xp
+    hi_act = _as_act(inp)
+    din = torch.empty_like(hi_act.data)
+    if st.wide:
+        sq.run(lambda: ops.wgrad3x3_wide(g, xp, conv.weight.grad, stride=stride), g)
+        if stride == 1:
+            ops.pad_bwd(ops.conv3_valid_adjoint(g, conv.weight, torch.empty_like(xp)), (1, 1, 1, 1), 0, din)
+        else:
+            ops.tconv3x3s2_wide(ops.pad_affine(g, (0, 1, 0, 1), 0), ops.w3x3_pack(conv.weight, "conv_s2_adj"), None, din)
+    elif stride == 1:
+        sq.run(lambda: ops.wgradk(g, hi_act, conv.weight.grad, pad=1, act_hi=inp_act), g)
+        ops.convk_bwd_data(g, conv.weight, din, pad=1)
+    else:
+        ci = conv.weight.shape[1]
+        dw4 = ops._w4_scratch(conv.weight.grad, 3, "grad")[0]
+        sq.run(lambda: (ops.wgrad4x4(g, hi_act, dw4, stride=2, pad=1, act_hi=inp_act, defer=False), ops.tap_extract(dw4, 3, 0, 0, conv.weight.grad)), g)
+        ops.conv4x4(g, ops.tap_embed3(conv.weight), 16, ci * 16, ci, din, stride=2, pad=1, transposed=True)
+    return _into_producer(din, inp, inp_act, bn_of)
 
 
-def _conv_valid3_bwd_data(g, conv, dp):
-    """dp (padded size) <- adjoint of _conv_valid3 w.r.t. its input"""
-    if _is_wide(conv):
-        q = ops.pad_affine(g, (2, 2, 2, 2), 0)
-        n, co, qh, qw = q.shape
-        if ops.conv3x3_wino_ok(n, co, dp.shape[1], qh - 2, qw - 2):
-            return ops.conv3x3_wino(q, ops.w3x3_wino_pack(conv.weight, "conv_adj"), None, dp)
-        return ops.conv3x3_wide(q, ops.w3x3_pack(conv.weight, "conv_adj"), None, dp)
-    return ops.convk_bwd_data(g, conv.weight, dp, pad=0)
+class ConvT3Ctx(_Step):
+    """ConvTranspose2d(3, stride 2, pad 1, output_padding 1) + norm + relu.  wide: on the GEMM-class kernels, z = the materialised act(inp)"""
+    __slots__ = ("conv", "inp", "inp_act", "out", "bn", "wide", "z")
 
 
-def _wgrad_valid3(g, p, conv):
-    """conv.weight.grad <- weight gradient of _conv_valid3"""
-    if _is_wide(conv):
-        return ops.wgrad3x3_wide(g, p, conv.weight.grad)
-    return ops.wgradk(g, p, conv.weight.grad, pad=0)
+def _convT3_forward(f, e, conv, bn):
+    st = ConvT3Ctx()
+    st.conv, st.bn, st.inp, st.inp_act, st.z = conv, bn, f.cur, f.pending, None
+    inp, inp_act, x = st.inp, st.inp_act, _as_act(f.cur).data
+    n, _, ih, iw = x.shape
+    co = conv.weight.shape[1]
+    r = _empty(n, co, 2 * ih, 2 * iw, x.device)
+    st.wide = ops.conv3_wide(conv.weight)
+    if st.wide:
+        st.z = ops.pad_affine(inp, (0, 0, 0, 0), 0, act=inp_act) if (inp_act or isinstance(inp, Act)) else inp
+        ops.tconv3x3s2_wide(ops.pad_affine(st.z, (0, 1, 0, 1), 0), ops.w3x3_pack(conv.weight, "convT_fwd"), conv.bias, r)
+    else:
+        ops.conv4x4(inp, ops.tap_embed3(conv.weight), 16, co * 16, co, r, bias=conv.bias, stride=2, pad=1, transposed=True, act_in=inp_act)
+    st.out = f.cur = _g_norm(f.G, r, bn)
+    f.pending = RELU
+    return st
 
 
-def _conv3(x, conv, out, stride, act_in):
-    if stride == 1:
-        return ops.convk(x, conv.weight, out, bias=conv.bias, pad=1, act_in=act_in)
-    w4 = ops.tap_embed(conv.weight, 3, 0, 0, ops._w4_scratch(conv.weight, 3, "fwd")[0])
-    co, ci = conv.weight.shape[:2]
-    return ops.conv4x4(x, w4, ci * 16, 16, co, out, bias=conv.bias, stride=2, pad=1, act_in=act_in)
+def _convT3_backward(st, g, sq, bn_of):
+    conv, inp, inp_act, z = st.conv, st.inp, st.inp_act, st.z
+    ci, co = conv.weight.shape[:2]
+    lo_act = _as_act(inp)
+    din = torch.empty_like(lo_act.data)
+    if st.wide:
+        gp = ops.pad_affine(g, (1, 1, 1, 1), 0)
+        sq.run(lambda: ops.wgrad3x3_wide(z, gp, conv.weight.grad, stride=2), gp)
+        ops.conv3x3s2_wide(gp, ops.w3x3_pack(conv.weight, "convT_adj"), None, din)
+    else:
+        dw4 = ops._w4_scratch(conv.weight.grad, 3, "grad")[0]
+        sq.run(lambda: (ops.wgrad4x4(lo_act, g, dw4, stride=2, pad=1, act_lo=inp_act, defer=False), ops.tap_extract(dw4, 3, 0, 0, conv.weight.grad)), g)
+        ops.conv4x4(g, ops.tap_embed3(conv.weight), co * 16, 16, ci, din, stride=2, pad=1)
+    return _into_producer(din, inp, inp_act, bn_of)
 
 
-def _seq_forward(G, seq, srcs, cur, pending, dropout_masks=None):
-    """Run one nn.Sequential-like segment (`seq.layout` over `seq.mod` / `seq.block_mods`).  srcs: the network input(s)
-    (Acts, concatenated on store into the first padded tensor) when the segment starts at the input (cur None);
-    otherwise cur is the incoming activation (Act with `pending` activation, or an identity tensor).
-    Returns (cur, pending, steps); steps hold what the backward needs.  G supplies the train / eval mode."""
-    first = srcs[0].data if cur is None else (cur.data if isinstance(cur, Act) else cur)
-    n, _, h, w = first.shape
-    dev = first.device
-    steps = []
-    lay = seq.layout
+class DownCtx(_Step):
+    """anti-aliased Downsample of inp = an Act, relu(norm(r)) on load"""
+    __slots__ = ("inp",)
+
+
+def _down_forward(f, e, *_):
+    st = DownCtx()
+    st.inp = f.cur
+    f.cur, f.pending = ops.blur_down(f.cur, act=f.pending), 0
+    return st
+
+
+def _down_backward(st, g, sq, bn_of):
+    da = torch.empty_like(st.inp.data)
+    ops.blur_down_bwd(g, da)
+    return _through_norm_relu(da, st.inp, bn_of.get(id(st.inp)))
+
+
+class UpCtx(_Step):
+    """anti-aliased Upsample of act(inp)"""
+    __slots__ = ("inp", "inp_act")
+
+
+def _up_forward(f, e, *_):
+    st = UpCtx()
+    st.inp, st.inp_act = f.cur, f.pending
+    f.cur, f.pending = ops.blur_up(f.cur, act=f.pending), 0
+    return st
+
+
+def _up_backward(st, g, sq, bn_of):
+    da = torch.empty_like(_as_act(st.inp).data)
+    ops.blur_up_bwd(g, da)
+    return _into_producer(da, st.inp, st.inp_act, bn_of)
+
+
+class BlockCtx(_Step):
+    """ResnetBlock, x + norm(conv(reflpad(relu(norm(conv(reflpad(x))))))): convolutions ca / cb with norms na / nb, padded operands
+    p1 / p2, normalised outputs a1 / a2.  src, src_act: what the identity input was materialised from (the first block behind a strided
+    conv), else None.  keep2: the Dropout map keep * 2, or None.  wide; wino / wino_adj: the forwards / the input adjoints take Winograd"""
+    __slots__ = ("ca", "cb", "na", "nb", "p1", "a1", "p2", "a2", "src", "src_act", "keep2", "wide", "wino", "wino_adj")
+
+    def weights(self):
+        return [self.ca.weight, self.cb.weight]
+
+
+def _block_forward(f, e, ca, na, cb, nb):
+    st = BlockCtx()
+    st.ca, st.na, st.cb, st.nb = ca, na, cb, nb
+    st.src = st.src_act = st.keep2 = None
+    if f.pending or isinstance(f.cur, Act):   # first block after a strided conv: materialise relu(norm(r))
+        st.src, st.src_act = f.cur, f.pending
+        f.cur, f.pending = ops.pad_affine(f.cur, (0, 0, 0, 0), 0, act=f.pending), 0
+    xb = f.cur           # identity tensor
+    n, c, h, w = xb.shape
+    dev = xb.device
+    st.wide = ops.conv3_wide(ca.weight)     # (both convolutions of a block are c -> c: one route, one pair of Winograd answers)
+    st.wino = st.wide and ops.conv3x3_wino_ok(n, c, c, h, w)
+    st.wino_adj = st.wide and ops.conv3x3_wino_ok(n, c, c, h + 2, w + 2)     # on the gradient zero-padded by 2
+    st.p1 = ops.pad_affine(xb, (1, 1, 1, 1), 1)
+    r1 = ops.conv3_valid(st.p1, ca.weight, ca.bias, _empty(n, c, h, w, dev), wino=st.wino)
+    st.a1 = _g_norm(f.G, r1, na)
+    if getattr(f.G, "use_dropout", False) and f.G.training:
+        # Dropout(0.5) between the ReLU and the second reflection pad (networks.py:1305-1306): relu(norm(r1)) is materialised,
+        # multiplied by keep * 2, and padded as a plain tensor; the backward multiplies by the same map
+        k = f.masks.pop(0) if f.masks else torch.bernoulli(torch.full(r1.shape, 0.5, device=dev))
+        st.keep2 = (k.to(device=dev, dtype=torch.float32) * 2.0).contiguous()
+        st.p2 = ops.pad_affine(_mask_mul(ops.pad_affine(st.a1, (0, 0, 0, 0), 0, act=RELU), st.keep2), (1, 1, 1, 1), 1)
+    else:
+        st.p2 = ops.pad_affine(st.a1, (1, 1, 1, 1), 1, act=RELU)
+    r2 = ops.conv3_valid(st.p2, cb.weight, cb.bias, _empty(n, c, h, w, dev), wino=st.wino)
+    st.a2 = _g_norm(f.G, r2, nb)
+    f.cur = ops.pad_affine(st.a2, (0, 0, 0, 0), 0, res=xb)
+    return st
+
+
+def _block_backward(st, g, sq, bn_of):
+    g2 = g.clone()
+    _g_norm_bwd(g2, st.a2, st.nb)
+    sq.run(lambda: ops.conv3_valid_wgrad(g2, st.p2, st.cb.weight.grad), g2)
+    dp2 = ops.conv3_valid_adjoint(g2, st.cb.weight, torch.empty_like(st.p2), wino=st.wino_adj)
+    da1 = ops.pad_bwd(dp2, (1, 1, 1, 1), 1, torch.empty_like(st.a1.data))
+    if st.keep2 is not None:      # Dropout backward
+        da1 = _mask_mul(da1, st.keep2)
+    g1 = _through_norm_relu(da1, st.a1, st.na)
+    sq.run(lambda: ops.conv3_valid_wgrad(g1, st.p1, st.ca.weight.grad), g1)
+    dp1 = ops.conv3_valid_adjoint(g1, st.ca.weight, torch.empty_like(st.p1), wino=st.wino_adj)
+    ops.pad_bwd(dp1, (1, 1, 1, 1), 1, g, accumulate=True)   # + the skip path, into the incoming gradient
+    return _into_producer(g, st.src, st.src_act, bn_of)
+
+
+_FORWARD_OF = {"conv7": _conv7_forward, "conv7_out": _conv7_out_forward, "conv3": _conv3_forward, "convT3": _convT3_forward,
+               "down": _down_forward, "up": _up_forward, "block": _block_forward}      # layout kind -> forward, record class -> backward
+_BACKWARD_OF = {Conv7Ctx: _conv7_backward, Conv7OutCtx: _conv7_out_backward, Conv3Ctx: _conv3_backward, ConvT3Ctx: _convT3_backward,
+                DownCtx: _down_backward, UpCtx: _up_backward, BlockCtx: _block_backward}
+
+
+def _seq_units(lay):
+    """a layout (the reference's nn.Sequential, entry by entry) as the units the engine runs: (kind, the unit's own entry, index of its
+    norm module | None).  The pad in front of a 7x7 convolution and the norm / relu / tanh entries behind a convolution are consumed here."""
     i = 0
-
-    def shape_of(t):
-        return (t.data if isinstance(t, Act) else t).shape
-
     while i < len(lay):
         e = lay[i]
         kind = e["kind"]
-        if kind == "pad":      # ReflectionPad2d(3) + conv7 (+ norm / relu | tanh)
-            conv = seq.mod(lay[i + 1]["idx"])
-            if cur is None:    # network input: concat the sources while padding
-                cin = sum(s_.data.shape[1] for s_ in srcs)
-                p = _empty(n, cin, h + 6, w + 6, dev)
-                c0 = 0
-                for s_ in srcs:
-                    c = s_.data.shape[1]
-                    ops.pad_affine(s_, (3, 3, 3, 3), 1, out=p[:, c0:c0 + c], out_nstride=p.stride(0))
-                    c0 += c
-                src_act = None
-            else:
-                p = ops.pad_affine(cur, (3, 3, 3, 3), 1, act=pending)
-                src_act = cur if isinstance(cur, Act) else None
-            r = _empty(n, conv.weight.shape[0], p.shape[2] - 6, p.shape[3] - 6, dev)
-            ops.convk(p, conv.weight, r, bias=conv.bias, pad=0)
-            if lay[i + 2]["kind"] == "norm":
-                bn = seq.mod(lay[i + 2]["idx"])
-                cur, pending = _g_norm(G, r, bn), RELU
-                steps.append(("conv7", conv, p, src_act, cur, bn))
-                i += 4
-            else:              # final conv + tanh
-                g_out = ops.pad_affine(r, (0, 0, 0, 0), 0, act=TANH)
-                steps.append(("conv7_out", conv, p, src_act, None, None))
-                i += 3
-                cur = g_out
-        elif kind == "conv3":  # Conv2d(3, pad 1, stride 1 | 2) + norm + relu
-            conv, bn = seq.mod(e["idx"]), seq.mod(lay[i + 1]["idx"])
-            inp, inp_act, stride = cur, pending, e["stride"]
-            _, _, ih, iw = shape_of(cur)
-            r = _empty(n, conv.weight.shape[0], (ih - 1) // stride + 1, (iw - 1) // stride + 1, dev)
-            if stride == 2 and (ih % 2 or iw % 2):
-                raise ValueError("stride-2 3x3 convolutions need even sizes, got %dx%d" % (ih, iw))
-            xp = None
-            if _is_wide(conv):     # GEMM-class kernels: materialise relu(norm(.)) with the zero padding once
-                xp = ops.pad_affine(inp, (1, 1, 1, 1), 0, act=inp_act)
-                wt = ops.w3x3_pack(conv.weight, "conv_fwd")
-                (ops.conv3x3_wide if stride == 1 else ops.conv3x3s2_wide)(xp, wt, conv.bias, r)
-            else:
-                _conv3(inp, conv, r, stride, inp_act)
-            cur, pending = _g_norm(G, r, bn), RELU
-            steps.append(("conv3", conv, inp, inp_act, cur, bn, stride, xp))
-            i += 3
-        elif kind == "convT3":  # ConvTranspose2d(3, stride 2, pad 1, output_padding 1) + norm + relu
-            conv, bn = seq.mod(e["idx"]), seq.mod(lay[i + 1]["idx"])
-            inp, inp_act = cur, pending
-            _, _, ih, iw = shape_of(cur)
-            ci, co = conv.weight.shape[:2]
-            r = _empty(n, co, 2 * ih, 2 * iw, dev)
-            z = None
-            if _is_wide(conv):
-                z = ops.pad_affine(inp, (0, 0, 0, 0), 0, act=inp_act) if (inp_act or isinstance(inp, Act)) else inp
-                ops.tconv3x3s2_wide(ops.pad_affine(z, (0, 1, 0, 1), 0), ops.w3x3_pack(conv.weight, "convT_fwd"), conv.bias, r)
-            else:
-                w4 = ops.tap_embed(conv.weight, 3, 0, 0, ops._w4_scratch(conv.weight, 3, "fwd")[0])
-                ops.conv4x4(inp, w4, 16, co * 16, co, r, bias=conv.bias, stride=2, pad=1, transposed=True, act_in=inp_act)
-            cur, pending = _g_norm(G, r, bn), RELU
-            steps.append(("convT3", conv, inp, inp_act, cur, bn, z))
-            i += 3
-        elif kind == "down":
-            inp = cur
-            cur, pending = ops.blur_down(cur, act=pending), 0
-            steps.append(("down", inp))
-            i += 1
-        elif kind == "up":
-            inp, inp_act = cur, pending
-            cur, pending = ops.blur_up(cur, act=pending), 0
-            steps.append(("up", inp, inp_act))
-            i += 1
-        elif kind == "block":  # x + norm(conv(reflpad(relu(norm(conv(reflpad(x)))))))
-            ca, na, cb, nb = seq.block_mods(e["idx"])
-            if pending or isinstance(cur, Act):   # first block after a strided conv: materialise relu(norm(r))
-                blk_src = (cur, pending)
-                cur, pending = ops.pad_affine(cur, (0, 0, 0, 0), 0, act=pending), 0
-            else:
-                blk_src = None
-            xb = cur           # identity tensor
-            p1 = ops.pad_affine(xb, (1, 1, 1, 1), 1)
-            r1 = _empty(n, ca.weight.shape[0], xb.shape[2], xb.shape[3], dev)
-            _conv_valid3(p1, ca, r1)
-            a1 = _g_norm(G, r1, na)
-            keep2 = None
-            if getattr(G, "use_dropout", False) and G.training:
-                # Dropout(0.5) between the ReLU and the second reflection pad (networks.py:1305-1306): relu(norm(r1)) is materialised,
-                # multiplied by keep * 2, and padded as a plain tensor; the backward multiplies by the same map
-                k = dropout_masks.pop(0) if dropout_masks else torch.bernoulli(torch.full(r1.shape, 0.5, device=dev))
-                keep2 = (k.to(device=dev, dtype=torch.float32) * 2.0).contiguous()
-                y1 = ops.pad_affine(a1, (0, 0, 0, 0), 0, act=RELU)
-                y1d = torch.empty_like(y1)
-                v = lambda t: t.view(-1, 1, t.shape[2], t.shape[3])
-                ops.mask_mul(v(y1), v(keep2), out=v(y1d))
-                p2 = ops.pad_affine(y1d, (1, 1, 1, 1), 1)
-            else:
-                p2 = ops.pad_affine(a1, (1, 1, 1, 1), 1, act=RELU)
-            r2 = _empty(n, cb.weight.shape[0], xb.shape[2], xb.shape[3], dev)
-            _conv_valid3(p2, cb, r2)
-            a2 = _g_norm(G, r2, nb)
-            cur, pending = ops.pad_affine(a2, (0, 0, 0, 0), 0, res=xb), 0
-            steps.append(("block", ca, cb, p1, a1, p2, a2, na, nb, blk_src, keep2))
-            i += 1
-        else:
+        if kind == "pad":      # ReflectionPad2d(3) + conv7 + (norm + relu | tanh)
+            i, e = i + 1, lay[i + 1]
+            kind = "conv7" if lay[i + 1]["kind"] == "norm" else "conv7_out"
+        if kind not in _FORWARD_OF:
             raise RuntimeError("unexpected layout entry %r" % (e,))
-    return cur, pending, steps
+        normed = kind in ("conv7", "conv3", "convT3")
+        yield kind, e, lay[i + 1]["idx"] if normed else None
+        i += 3 if normed else 2 if kind == "conv7_out" else 1
+
+
+def _seq_forward(G, seq, srcs, cur, pending, dropout_masks=None):
+    """Run one nn.Sequential-like segment (`seq.layout` over `seq.mod` / `seq.block_mods`).  srcs: the network input(s) (Acts, concatenated on
+    store into the first padded tensor) when the segment starts at the input (cur None); otherwise cur is the incoming activation (Act with `pending`
+    activation, or an identity tensor).  Returns (cur, pending, steps); steps: one record per layer.  G supplies the train / eval mode."""
+    f = _Flow()
+    f.G, f.cur, f.pending, f.srcs, f.masks = G, cur, pending, srcs, dropout_masks
+    steps = []
+    for kind, e, norm_idx in _seq_units(seq.layout):
+        mods = seq.block_mods(e["idx"]) if kind == "block" else (seq.mod(e["idx"]), None if norm_idx is None else seq.mod(norm_idx))
+        steps.append(_FORWARD_OF[kind](f, e, *mods))
+    return f.cur, f.pending, steps
+
+
+def _seq_backward(steps, g, sq, bn_of, start=0, stop=None):
+    """backward of one segment: g = gradient w.r.t. its output (the pre-tanh output for a final conv7, else w.r.t. the raw output of its last conv /
+    the identity output of its last block).  Writes the parameters' .grad (overwrite; through the side queue sq) and returns the gradient flowing
+    into the layer below the segment.  start / stop: only steps[start:stop] (the stages of resnet_backward_stage)."""
+    for st in reversed(steps[start:stop]):
+        g = _BACKWARD_OF[type(st)](st, g, sq, bn_of)
+    return g
+
+
+def _bn_map(*step_lists):
+    """Act -> the BatchNorm module that produced its affine (None: InstanceNorm)"""
+    return {id(st.out): st.bn for steps in step_lists for st in steps if st.out is not None}
 
 
 def resnet_forward(G, x, keep=True, dropout_masks=None):
@@ -1034,11 +1196,13 @@ def resnet_forward(G, x, keep=True, dropout_masks=None):
         return local_enhancer_forward(G, x, keep)
     srcs = [_as_act(t) for t in (x if isinstance(x, (tuple, list)) else (x,))]
     cur, _, steps = _seq_forward(G, G, srcs, None, 0, dropout_masks=list(dropout_masks) if dropout_masks else None)
-    ctx = None
-    if keep:
-        ctx = ResnetCtx()
-        ctx.steps, ctx.g_out = steps, cur
-    return cur, ctx
+    return cur, (ResnetCtx(steps, cur) if keep else None)
+
+
+class LocalLevelCtx:
+    """one enhancer of a LocalEnhancer: the steps of model<n>_1 (down) and model<n>_2 (up), which runs on relu(norm(a)) + relu(norm(b)) --
+    a: the output of the level below, b: the output of `down`"""
+    __slots__ = ("down", "up", "a", "b")
 
 
 def local_enhancer_forward(G, x, keep=True):
@@ -1052,138 +1216,14 @@ def local_enhancer_forward(G, x, keep=True):
     a, pa, steps_g = _seq_forward(G, G.seq_global, [pyr[-1]], None, 0)
     levels = []
     for n in range(1, L + 1):
-        b, pb, steps_1 = _seq_forward(G, G.seq_down[n - 1], [pyr[L - n]], None, 0)
-        bm = ops.pad_affine(b, (0, 0, 0, 0), 0, act=pb)
+        lv = LocalLevelCtx()
+        lv.a = a
+        lv.b, pb, lv.down = _seq_forward(G, G.seq_down[n - 1], [pyr[L - n]], None, 0)
+        bm = ops.pad_affine(lv.b, (0, 0, 0, 0), 0, act=pb)
         s = ops.pad_affine(a, (0, 0, 0, 0), 0, act=pa, res=bm)
-        out, pout, steps_2 = _seq_forward(G, G.seq_up[n - 1], None, s, 0)
-        levels.append((steps_1, steps_2, a, b))
-        a, pa = out, pout
-    ctx = None
-    if keep:
-        ctx = ResnetCtx()
-        ctx.steps, ctx.g_out = (steps_g, levels), a
-    return a, ctx
-
-
-def _through_norm_relu(g_act, a, bn):
-    """gradient w.r.t. relu(norm(r)) -> gradient w.r.t. the raw conv output r (in a fresh buffer)"""
-    buf = torch.empty_like(a.data)
-    ops.act_bwd(g_act, a, RELU, buf)
-    _g_norm_bwd(buf, a, bn)
-    return buf
-
-
-def _bn_map(*step_lists):
-    """Act -> the BatchNorm module that produced its affine (None: InstanceNorm)"""
-    bn_of = {}
-    for steps in step_lists:
-        for st in steps:
-            if st[0] in ("conv7", "conv3", "convT3"):
-                bn_of[id(st[4])] = st[5]
-    return bn_of
-
-
-def _seq_backward(steps, g, sq, bn_of, start=0, stop=None):
-    """backward of one segment: g = gradient w.r.t. its output (the pre-tanh output for a final conv7, else w.r.t. the
-    raw output of its last conv / the identity output of its last block).  Writes the parameters' .grad (overwrite;
-    through the side queue sq) and returns the gradient w.r.t. the segment's input (None for a network input).
-    start / stop: only steps[start:stop] (the stages of resnet_backward_stage)."""
-    dev = g.device
-    through_norm_relu = _through_norm_relu
-
-    def producer_bn(a):
-        return bn_of.get(id(a))
-
-    for st in reversed(steps[start:stop]):
-        kind = st[0]
-        if kind == "conv7_out":
-            _, conv, p, src_act, _, _ = st
-            sq.run(lambda: (ops.wgradk(g, p, conv.weight.grad, pad=0), ops.channel_sum(g, conv.bias.grad)), g)
-            dp = torch.empty_like(p)
-            ops.convk_bwd_data(g, conv.weight, dp, pad=0)
-            da = _empty(p.shape[0], p.shape[1], p.shape[2] - 6, p.shape[3] - 6, dev)
-            ops.pad_bwd(dp, (3, 3, 3, 3), 1, da)
-            g = through_norm_relu(da, src_act, producer_bn(src_act))   # the padded tensor was relu(norm(r_prev))
-        elif kind == "conv7":
-            _, conv, p, src_act, a, bn = st
-            sq.run(lambda: ops.wgradk(g, p, conv.weight.grad, pad=0), g)  # network input: no gradient needed below
-        elif kind == "conv3":
-            _, conv, inp, inp_act, a, bn, stride, xp = st
-            hi_act = inp if isinstance(inp, Act) else Act(inp)
-            t = inp.data if isinstance(inp, Act) else inp
-            din = torch.empty_like(t)
-            if xp is not None:     # wide layer
-                sq.run(lambda: ops.wgrad3x3_wide(g, xp, conv.weight.grad, stride=stride), g)
-                if stride == 1:
-                    dxp = torch.empty_like(xp)
-                    ops.conv3x3_wide(ops.pad_affine(g, (2, 2, 2, 2), 0), ops.w3x3_pack(conv.weight, "conv_adj"), None, dxp)
-                    ops.pad_bwd(dxp, (1, 1, 1, 1), 0, din)
-                else:
-                    ops.tconv3x3s2_wide(ops.pad_affine(g, (0, 1, 0, 1), 0), ops.w3x3_pack(conv.weight, "conv_s2_adj"), None, din)
-            elif stride == 1:
-                sq.run(lambda: ops.wgradk(g, hi_act, conv.weight.grad, pad=1, act_hi=inp_act), g)
-                ops.convk_bwd_data(g, conv.weight, din, pad=1)
-            else:
-                co, ci = conv.weight.shape[:2]
-                dw4 = ops._w4_scratch(conv.weight.grad, 3, "grad")[0]
-                sq.run(lambda: (ops.wgrad4x4(g, hi_act, dw4, stride=2, pad=1, act_hi=inp_act, defer=False), ops.tap_extract(dw4, 3, 0, 0, conv.weight.grad)), g)
-                w4 = ops.tap_embed(conv.weight, 3, 0, 0, ops._w4_scratch(conv.weight, 3, "fwd")[0])
-                ops.conv4x4(g, w4, 16, ci * 16, ci, din, stride=2, pad=1, transposed=True)
-            g = through_norm_relu(din, inp, producer_bn(inp)) if inp_act == RELU else din
-        elif kind == "convT3":
-            _, conv, inp, inp_act, a, bn, z = st
-            ci, co = conv.weight.shape[:2]
-            lo_act = inp if isinstance(inp, Act) else Act(inp)
-            t = inp.data if isinstance(inp, Act) else inp
-            din = torch.empty_like(t)
-            if z is not None:      # wide layer
-                gp = ops.pad_affine(g, (1, 1, 1, 1), 0)
-                sq.run(lambda: ops.wgrad3x3_wide(z, gp, conv.weight.grad, stride=2), gp)
-                ops.conv3x3s2_wide(gp, ops.w3x3_pack(conv.weight, "convT_adj"), None, din)
-            else:
-                dw4 = ops._w4_scratch(conv.weight.grad, 3, "grad")[0]
-                sq.run(lambda: (ops.wgrad4x4(lo_act, g, dw4, stride=2, pad=1, act_lo=inp_act, defer=False), ops.tap_extract(dw4, 3, 0, 0, conv.weight.grad)), g)
-                w4 = ops.tap_embed(conv.weight, 3, 0, 0, ops._w4_scratch(conv.weight, 3, "fwd")[0])
-                ops.conv4x4(g, w4, co * 16, 16, ci, din, stride=2, pad=1)
-            g = through_norm_relu(din, inp, producer_bn(inp)) if inp_act == RELU else din
-        elif kind == "down":
-            inp = st[1]       # Act: relu(norm(r)) on load
-            da = torch.empty_like(inp.data)
-            ops.blur_down_bwd(g, da)
-            g = through_norm_relu(da, inp, producer_bn(inp))
-        elif kind == "up":
-            _, inp, inp_act = st
-            t = inp.data if isinstance(inp, Act) else inp
-            da = torch.empty_like(t)
-            ops.blur_up_bwd(g, da)
-            g = through_norm_relu(da, inp, producer_bn(inp)) if inp_act == RELU else da
-        elif kind == "block":
-            _, ca, cb, p1, a1, p2, a2, na, nb, blk_src, keep2 = st
-            dy = g
-            g2 = dy.clone()
-            _g_norm_bwd(g2, a2, nb)
-            sq.run(lambda: _wgrad_valid3(g2, p2, cb), g2)
-            dp2 = torch.empty_like(p2)
-            _conv_valid3_bwd_data(g2, cb, dp2)
-            da1 = torch.empty_like(a1.data)
-            ops.pad_bwd(dp2, (1, 1, 1, 1), 1, da1)
-            if keep2 is not None:      # Dropout backward
-                dd = torch.empty_like(da1)
-                v = lambda t: t.view(-1, 1, t.shape[2], t.shape[3])
-                ops.mask_mul(v(da1), v(keep2), out=v(dd))
-                da1 = dd
-            g1 = through_norm_relu(da1, a1, na)
-            sq.run(lambda: _wgrad_valid3(g1, p1, ca), g1)
-            dp1 = torch.empty_like(p1)
-            _conv_valid3_bwd_data(g1, ca, dp1)
-            ops.pad_bwd(dp1, (1, 1, 1, 1), 1, dy, accumulate=True)   # + the skip path
-            g = dy
-            if blk_src is not None:    # the block input was materialised from relu(norm(r)) of a strided conv
-                src, src_act = blk_src
-                g = through_norm_relu(g, src, producer_bn(src)) if src_act == RELU else g
-        else:
-            raise RuntimeError(kind)
-    return g
+        a, pa, lv.up = _seq_forward(G, G.seq_up[n - 1], None, s, 0)
+        levels.append(lv)
+    return a, (ResnetCtx((steps_g, levels), a) if keep else None)
 
 
 def resnet_backward(G, ctx, d_raw):
@@ -1192,25 +1232,16 @@ def resnet_backward(G, ctx, d_raw):
     sq = SideQueue()     # weight / bias gradients: off the critical path of the backward-data chain
     if getattr(G, "is_local_enhancer", False):
         steps_g, levels = ctx.steps
-        bn_of = _bn_map(steps_g, *[lv[0] for lv in levels], *[lv[1] for lv in levels])
+        bn_of = _bn_map(steps_g, *[lv.down for lv in levels], *[lv.up for lv in levels])
         g = d_raw
-        for steps_1, steps_2, a, b in reversed(levels):
-            g_s = _seq_backward(steps_2, g, sq, bn_of)         # gradient w.r.t. relu(norm(a)) + relu(norm(b))
-            _seq_backward(steps_1, _through_norm_relu(g_s, b, bn_of.get(id(b))), sq, bn_of)
-            g = _through_norm_relu(g_s, a, bn_of.get(id(a)))   # ... w.r.t. the raw output of the level below
+        for lv in reversed(levels):
+            g_s = _seq_backward(lv.up, g, sq, bn_of)         # gradient w.r.t. relu(norm(a)) + relu(norm(b))
+            _seq_backward(lv.down, _through_norm_relu(g_s, lv.b, bn_of.get(id(lv.b))), sq, bn_of)
+            g = _through_norm_relu(g_s, lv.a, bn_of.get(id(lv.a)))   # ... w.r.t. the raw output of the level below
         _seq_backward(steps_g, g, sq, bn_of)
     else:
         _seq_backward(ctx.steps, d_raw, sq, _bn_map(ctx.steps))
     sq.join()
-
-
-def _step_weights(st):
-    """the convolution weights a step of a ResNet-family generator owns"""
-    if st[0] in ("conv7_out", "conv7", "conv3", "convT3"):
-        return [st[1].weight]
-    if st[0] == "block":
-        return [st[1].weight, st[2].weight]
-    return []
 
 
 def resnet_stage_bounds(ctx, cut_params):
@@ -1219,10 +1250,7 @@ def resnet_stage_bounds(ctx, cut_params):
     starts at a convolution weight).  A bucket that starts inside a two-convolution block is complete after the stage that holds the
     block (the block's first convolution then belongs to the next bucket down and is simply early).  Returns [0, s_1, .., s_K-1, len(steps)]."""
     steps = ctx.steps
-    where = {}
-    for i, st in enumerate(steps):
-        for w in _step_weights(st):
-            where[w.data_ptr()] = i
+    where = {w.data_ptr(): i for i, st in enumerate(steps) for w in st.weights()}
     bounds = [0]
     for p in cut_params:
         i = where.get(p.data_ptr())
@@ -2583,38 +2611,10 @@ def tactile_patch_fid(real_T, fake_T, reduction="none", clamp_fake=True):
 
 # ======================================================================================================================
 # SPADE generator (`--netG spade`; reference models/networks.py:2075-2200, models/architecture.py:21-68, models/normalization.py:68-112)
-# Every 3x3 convolution reads a pre-padded operand (the modulate kernel stores that layout directly); layers of >= 64 x 64 channels
-# run on the GEMM-class kernels, the rest (label_nc = 1 inputs, the output_nc-channel image head, the 1x1 shortcut) on the 4x4 family.
+# Every 3x3 convolution reads a pre-padded operand (the modulate kernel stores that layout directly) through conv3_valid and its adjoint /
+# weight gradient, the dispatch of the ResNet blocks, never on Winograd: layers of >= 64 x 64 channels run on the GEMM-class kernels,
+# the rest (label_nc = 1 inputs, the output_nc-channel image head) and the 1x1 shortcut on the 4x4 family.
 # ======================================================================================================================
-def _sp_wide(w):
-    co, ci, k = w.shape[0], w.shape[1], w.shape[2]
-    return k == 3 and co >= 64 and ci >= 64 and co % 4 == 0 and ci % 4 == 0
-
-
-def _sp_conv(p, w, b, out, act_out=0):
-    """out [N,Co,H,W] <- act_out(valid 3x3 convolution of the pre-padded p [N,Ci,H+2,W+2] + b)"""
-    if _sp_wide(w):
-        if act_out:
-            raise NotImplementedError("an output activation on the GEMM-class 3x3 convolution (an image head of >= 64 channels)")
-        return ops.conv3x3_wide(p, ops.w3x3_pack(w, "conv_fwd"), b, out)
-    co, ci = w.shape[:2]
-    w4 = ops.tap_embed(w, 3, 0, 0, ops._w4_scratch(w, 3, "fwd")[0])
-    return ops.conv4x4(p, w4, ci * 16, 16, co, out, bias=b, stride=1, pad=0, act_out=act_out)
-
-
-def _sp_conv_bwd_data(g, w, dp):
-    """dp [N,Ci,H+2,W+2] <- adjoint of _sp_conv w.r.t. its padded operand"""
-    if _sp_wide(w):
-        return ops.conv3x3_wide(ops.pad_affine(g, (2, 2, 2, 2), 0), ops.w3x3_pack(w, "conv_adj"), None, dp)
-    return ops.convk_bwd_data(g, w, dp, pad=0)
-
-
-def _sp_wgrad(g, p, dw):
-    if _sp_wide(dw):
-        return ops.wgrad3x3_wide(g, p, dw)
-    return ops.wgradk(g, p, dw, pad=0)
-
-
 class _SnState:
     """what one spectral-normalised convolution keeps between the generator's forward and backward: W / sigma, sigma, a gradient buffer"""
     __slots__ = ("w", "sigma", "g")
@@ -2653,7 +2653,7 @@ def _sp_param_grads(conv, g, p, k3=True):
     sn = hasattr(conv, "weight_u")
     dw = _sn_state(conv).g if sn else _grad(conv.weight)
     if k3:
-        _sp_wgrad(g, p, dw)
+        ops.conv3_valid_wgrad(g, p, dw)
     else:
         ops.wgradk(g, p, dw, pad=0)
     if sn:
@@ -2697,11 +2697,11 @@ def spade_norm_forward(m, x, seg, act=0, out_pad=0, keep=True, cache=None, train
     s_pad = _seg_at(seg, h, w, cache)
     sh = getattr(m.mlp_shared, "0")
     a_raw = _empty(n, m.NHIDDEN, h, w, x.device)
-    _sp_conv(s_pad, sh.weight, sh.bias, a_raw)
+    ops.conv3_valid(s_pad, sh.weight, sh.bias, a_raw)
     p_act = ops.pad_affine(a_raw, (1, 1, 1, 1), 0, act=RELU)
     gamma, beta = _empty(n, c, h, w, x.device), _empty(n, c, h, w, x.device)
-    _sp_conv(p_act, m.mlp_gamma.weight, m.mlp_gamma.bias, gamma)
-    _sp_conv(p_act, m.mlp_beta.weight, m.mlp_beta.bias, beta)
+    ops.conv3_valid(p_act, m.mlp_gamma.weight, m.mlp_gamma.bias, gamma)
+    ops.conv3_valid(p_act, m.mlp_beta.weight, m.mlp_beta.bias, beta)
     out = ops.spade_modulate(x, mean, rstd, gamma, beta, act=act, out_pad=out_pad)
     if not keep:
         return out, None
@@ -2722,17 +2722,17 @@ def spade_norm_backward(m, ctx, g, g_pad=0, dsegs=None, want_dseg=True):
     da_sum = _empty(n, m.NHIDDEN, h, w, dev)
     for i, (conv, dmap) in enumerate(((m.mlp_gamma, dgamma), (m.mlp_beta, dbeta))):
         ops.channel_sum(dmap, _grad(conv.bias))
-        _sp_wgrad(dmap, ctx.p_act, _grad(conv.weight))
-        dp = _sp_conv_bwd_data(dmap, conv.weight, _empty(n, m.NHIDDEN, h + 2, w + 2, dev))
+        ops.conv3_valid_wgrad(dmap, ctx.p_act, _grad(conv.weight))
+        dp = ops.conv3_valid_adjoint(dmap, conv.weight, _empty(n, m.NHIDDEN, h + 2, w + 2, dev))
         ops.pad_bwd(dp, (1, 1, 1, 1), 0, da_sum, accumulate=i > 0)
     da = _empty(n, m.NHIDDEN, h, w, dev)
     ops.act_bwd(da_sum, ctx.a_raw, RELU, da)
     sh = getattr(m.mlp_shared, "0")
     ops.channel_sum(da, _grad(sh.bias))
-    _sp_wgrad(da, ctx.s_pad, _grad(sh.weight))
+    ops.conv3_valid_wgrad(da, ctx.s_pad, _grad(sh.weight))
     if not want_dseg:
         return dx, None
-    dsp = _sp_conv_bwd_data(da, sh.weight, _empty(n, ctx.seg_shape[1], h + 2, w + 2, dev))
+    dsp = ops.conv3_valid_adjoint(da, sh.weight, _empty(n, ctx.seg_shape[1], h + 2, w + 2, dev))
     own = dsegs is None
     if own:
         dsegs = {}
@@ -2772,9 +2772,9 @@ def spade_block_forward(blk, x, seg, keep=True, cache=None, weights_ready=False)
         x_s = x
     w0, w1 = _sp_weight(blk.conv_0), _sp_weight(blk.conv_1)
     ctx.p0, ctx.n0 = spade_norm_forward(blk.norm_0, x, seg, act=LRELU, out_pad=1, keep=keep, cache=cache, training=blk.training)
-    d0 = _sp_conv(ctx.p0, w0, blk.conv_0.bias, _empty(n, w0.shape[0], h, w, dev))
+    d0 = ops.conv3_valid(ctx.p0, w0, blk.conv_0.bias, _empty(n, w0.shape[0], h, w, dev))
     ctx.p1, ctx.n1 = spade_norm_forward(blk.norm_1, d0, seg, act=LRELU, out_pad=1, keep=keep, cache=cache, training=blk.training)
-    d1 = _sp_conv(ctx.p1, w1, blk.conv_1.bias, _empty(n, w1.shape[0], h, w, dev))
+    d1 = ops.conv3_valid(ctx.p1, w1, blk.conv_1.bias, _empty(n, w1.shape[0], h, w, dev))
     out = ops.pad_affine(d1, (0, 0, 0, 0), 0, res=x_s)
     return out, (ctx if keep else None)
 
@@ -2790,10 +2790,10 @@ def spade_block_backward(blk, ctx, g, dsegs=None, want_dseg=True):
         dsegs = {}
     w0, w1 = _sp_weight(blk.conv_0), _sp_weight(blk.conv_1)
     _sp_param_grads(blk.conv_1, g, ctx.p1)
-    dp1 = _sp_conv_bwd_data(g, w1, _empty(n, w1.shape[1], h + 2, w + 2, dev))
+    dp1 = ops.conv3_valid_adjoint(g, w1, _empty(n, w1.shape[1], h + 2, w + 2, dev))
     dd0, _ = spade_norm_backward(blk.norm_1, ctx.n1, dp1, g_pad=1, dsegs=dsegs, want_dseg=want_dseg)
     _sp_param_grads(blk.conv_0, dd0, ctx.p0)
-    dp0 = _sp_conv_bwd_data(dd0, w0, _empty(n, fin, h + 2, w + 2, dev))
+    dp0 = ops.conv3_valid_adjoint(dd0, w0, _empty(n, fin, h + 2, w + 2, dev))
     dx, _ = spade_norm_backward(blk.norm_0, ctx.n0, dp0, g_pad=1, dsegs=dsegs, want_dseg=want_dseg)
     if blk.learned_shortcut:
         ws = _sp_weight(blk.conv_s)
@@ -2833,7 +2833,7 @@ def spade_forward(G, seg, keep=True):
     ctx = SpadeCtx()
     ctx.seg_shape = tuple(seg.shape)
     ctx.s0_pad = _seg_at(seg, G.sh, G.sw, cache)
-    x = _sp_conv(ctx.s0_pad, G.fc.weight, G.fc.bias, _empty(n, G.fc.weight.shape[0], G.sh, G.sw, dev))
+    x = ops.conv3_valid(ctx.s0_pad, G.fc.weight, G.fc.bias, _empty(n, G.fc.weight.shape[0], G.sh, G.sw, dev))
     ctx.blocks = []
     for blk, up in _spade_plan(G):
         if up:
@@ -2842,7 +2842,7 @@ def spade_forward(G, seg, keep=True):
         ctx.blocks.append(bctx)
     ctx.x_last = x
     ctx.p_last = ops.pad_affine(x, (1, 1, 1, 1), 0, act=LRELU)
-    out = _sp_conv(ctx.p_last, G.conv_img.weight, G.conv_img.bias, _empty(n, G.conv_img.weight.shape[0], x.shape[2], x.shape[3], dev), act_out=TANH)
+    out = ops.conv3_valid(ctx.p_last, G.conv_img.weight, G.conv_img.bias, _empty(n, G.conv_img.weight.shape[0], x.shape[2], x.shape[3], dev), act_out=TANH)
     ctx.out = out
     return out, (ctx if keep else None)
 
@@ -2857,8 +2857,8 @@ def spade_backward(G, ctx, dout, want_dseg=True, pre_tanh=False):
     x = ctx.x_last
     dz = dout.contiguous() if pre_tanh else ops.tanh_bwd(dout.contiguous(), ctx.out)
     ops.channel_sum(dz, _grad(G.conv_img.bias))
-    _sp_wgrad(dz, ctx.p_last, _grad(G.conv_img.weight))
-    dp = _sp_conv_bwd_data(dz, G.conv_img.weight, _empty(n, x.shape[1], x.shape[2] + 2, x.shape[3] + 2, dev))
+    ops.conv3_valid_wgrad(dz, ctx.p_last, _grad(G.conv_img.weight))
+    dp = ops.conv3_valid_adjoint(dz, G.conv_img.weight, _empty(n, x.shape[1], x.shape[2] + 2, x.shape[3] + 2, dev))
     gc = ops.pad_bwd(dp, (1, 1, 1, 1), 0, torch.empty_like(x))
     g = ops.act_bwd(gc, x, LRELU, torch.empty_like(x))
     dsegs = {}
@@ -2867,10 +2867,10 @@ def spade_backward(G, ctx, dout, want_dseg=True, pre_tanh=False):
         if up:
             g = ops.nearest_up2_bwd(g)
     ops.channel_sum(g, _grad(G.fc.bias))
-    _sp_wgrad(g, ctx.s0_pad, _grad(G.fc.weight))
+    ops.conv3_valid_wgrad(g, ctx.s0_pad, _grad(G.fc.weight))
     if not want_dseg:
         return None
-    ds0 = _sp_conv_bwd_data(g, G.fc.weight, _empty(n, ctx.seg_shape[1], G.sh + 2, G.sw + 2, dev))
+    ds0 = ops.conv3_valid_adjoint(g, G.fc.weight, _empty(n, ctx.seg_shape[1], G.sh + 2, G.sw + 2, dev))
     acc = dsegs.get((G.sh, G.sw))
     if acc is None:
         dsegs[(G.sh, G.sw)] = ops.pad_bwd(ds0, (1, 1, 1, 1), 0, _empty(n, ctx.seg_shape[1], G.sh, G.sw, dev))

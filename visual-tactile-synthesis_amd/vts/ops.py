@@ -818,6 +818,49 @@ def wgrad3x3_wide(dout, p, dw, accumulate=False, stride=1):
     return dw
 
 
+# ---- valid 3x3 convolution of a pre-padded operand: the one dispatch of the ResNet blocks and of the SPADE generator (vts/engine.py) ----
+def conv3_wide(w):
+    """the kernel route of a 3x3 layer, asked once (in its forward): the GEMM-class kernels (vts_conv3x3_wide family) pay from
+    64 x 64 channels, multiples of 4; below, one 4x4 tap block.  w: a Conv2d or ConvTranspose2d weight (the rule is symmetric)"""
+    a, b, k = w.shape[0], w.shape[1], w.shape[2]
+    return k == 3 and a >= 64 and b >= 64 and a % 4 == 0 and b % 4 == 0
+
+
+def tap_embed3(w):
+    """the 3x3 weight w embedded in its one 4x4 tap block (persistent staging buffer)"""
+    return tap_embed(w, 3, 0, 0, _w4_scratch(w, 3, "fwd")[0])
+
+
+def conv3_valid(p, w, bias, out, act_out=0, wino=False):
+    """out [N,Co,H,W] <- act_out(valid 3x3 convolution of the pre-padded p [N,Ci,H+2,W+2] with the weight tensor w, + bias).
+    wino: a wide layer takes Winograd F(2x2, 3x3) -- 1.5 - 1.9x the direct kernel (round 4); the caller asked conv3x3_wino_ok"""
+    if conv3_wide(w):
+        if act_out:
+            raise NotImplementedError("an output activation on the GEMM-class 3x3 convolution (an image head of >= 64 channels)")
+        if wino:
+            return conv3x3_wino(p, w3x3_wino_pack(w, "conv_fwd"), bias, out)
+        return conv3x3_wide(p, w3x3_pack(w, "conv_fwd"), bias, out)
+    co, ci = w.shape[:2]
+    return conv4x4(p, tap_embed3(w), ci * 16, 16, co, out, bias=bias, stride=1, pad=0, act_out=act_out)
+
+
+def conv3_valid_adjoint(g, w, dp, wino=False):
+    """dp [N,Ci,H+2,W+2] <- adjoint of conv3_valid w.r.t. its padded operand; wino as there, asked for the shape of g zero-padded by 2"""
+    if conv3_wide(w):
+        q = pad_affine(g, (2, 2, 2, 2), 0)
+        if wino:
+            return conv3x3_wino(q, w3x3_wino_pack(w, "conv_adj"), None, dp)
+        return conv3x3_wide(q, w3x3_pack(w, "conv_adj"), None, dp)
+    return convk_bwd_data(g, w, dp, pad=0)
+
+
+def conv3_valid_wgrad(g, p, dw):
+    """dw [Co,Ci,3,3] <- weight gradient of conv3_valid"""
+    if conv3_wide(dw):
+        return wgrad3x3_wide(g, p, dw)
+    return wgradk(g, p, dw, pad=0)
+
+
 def w4x4_pack(w, mode, tag=None):
     """tap-major packing of an nn.Conv2d weight [Co,Ci,4,4] for conv4x4_flat (see include/vts.h) into a persistent buffer"""
     d0, d1 = w.shape[0], w.shape[1]

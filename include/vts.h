@@ -637,6 +637,27 @@ int vts_ganloss(const float* pred, int N, int M, int mode, int target_is_real, f
 int vts_l1(const float* a, const float* b, int64_t n, float coeff, int64_t* loss_out, float* grad, int accumulate,
            void* stream);
 
+/* WGAN-GP gradient penalty (models/networks.py:550-583, cal_gradient_penalty with type 'mixed'); csrc/vts_gradpen.hip.
+ * vts_gp_interp    out[n] = alpha[n] * real[n] + (1 - alpha[n]) * fake[n]  (:568-571), out contiguous [N, C, HW].  `real` and `fake` are
+ *                  each torch.cat([x0, x1], 1) read in place: x0 / x1 are channel slices with their own sample stride and channel count
+ *                  (x1 NULL with 0 channels: one source); both sides have C channels in all, the split may differ.  alpha: device [N].
+ *                  Instance gp_interp_kernel.
+ * vts_gp_penalty   for the input gradient g [N, M] of the discriminator at `out` (:575-582), norm_n = || g_n + 1e-16 ||_2:
+ *                    value[0]         = P = lambda_gp / N * sum_n (norm_n - constant)^2                      (optional)
+ *                    loss_out[0]     += coeff * P    in the slots' fixed point (VTS_LOSS_SCALE)             (optional)
+ *                    scale[n * C + c] = grad_coeff * 2 lambda_gp / N * (norm_n - constant) / norm_n,  shift[n * C + c] = scale * 1e-16:
+ *                  the cotangent grad_coeff * dP/dg = scale * g + shift as a per-(n, c) operand affine of g viewed as [N, C, M / C], for
+ *                  the first convolution of the tangent pass to apply on load.  The squares are summed in double, in blocks of 4096
+ *                  elements on at most 256 workgroups per sample (a workgroup walks blocks w, w + 256, ... in order), the partials
+ *                  (`ws`, 8-byte aligned, vts_gp_penalty_ws_floats) by a second launch in index order: no float atomics, a second call
+ *                  gives the same bits.  Instance "gp_sumsq_kernel[<blocks per sample> blocks on <workgroups per sample> workgroups]+gp_finish_kernel". */
+int vts_gp_interp(const float* real0, int64_t real0_nstride, int real0_c, const float* real1, int64_t real1_nstride, int real1_c,
+                  const float* fake0, int64_t fake0_nstride, int fake0_c, const float* fake1, int64_t fake1_nstride, int fake1_c,
+                  const float* alpha, int N, int64_t HW, float* out, void* stream);
+int64_t vts_gp_penalty_ws_floats(int N, int64_t M);
+int vts_gp_penalty(const float* g, int N, int64_t M, int C, float lambda_gp, float constant, float coeff, float grad_coeff,
+                   int64_t* loss_out, float* value, float* scale, float* shift, float* ws, void* stream);
+
 /* Patch gather with clamp-to-border (models/model_utils.py:252-333), for P patches of
  * size x size taken from image index img[p] at offsets (offx[p], offy[p]):
  *   out[p, out_c0 + c, y, x] = src[img[p], c, clamp(offy+y), clamp(offx+x)]

@@ -164,8 +164,7 @@ class SinSKITGModel(GraphedStepModel):
             self.criterionGAN = networks.GANLoss(opt.gan_mode, target_real_label=0.8, target_fake_label=0.0)
         else:
             self.criterionGAN = networks.GANLoss(opt.gan_mode)
-        if opt.gan_mode == "wgangp":
-            raise NotImplementedError("gan_mode wgangp needs a double-backward gradient penalty; not built")
+        self._check_wgangp(opt)
 
         self.pe_channels = 2 * opt.positional_encoding_dim if opt.use_positional_encoding else 0
         if opt.use_positional_encoding and opt.positional_encoding_mode != "spe":
@@ -250,6 +249,31 @@ class SinSKITGModel(GraphedStepModel):
             raise RuntimeError("VTS_KO_LANES skips discriminator lanes (wrong losses and gradients): set VTS_KO_LANES_ACK=timing-only to run the timing experiment")
         self._draws = None      # tests / parity runs inject {"aug": [4,N], "more_idx": [N,K]}
         self.style_code = None
+
+    @staticmethod
+    def _check_wgangp(opt):
+        """--gan_mode wgangp: the WGAN loss plus cal_gradient_penalty on D1 (sinskitG_model.py:1377-1387; engine.sg2d_gradient_penalty).
+        Probed on the reference (CPU, 256 x 256, batch 1): it trains in exactly one configuration, the StyleGAN2 discriminator on the
+        image and no tactile discriminator; that one is accepted, every other raises with what the reference does there."""
+        if getattr(opt, "gan_mode", None) != "wgangp" or not opt.isTrain:
+            return
+        if opt.lambda_G1_GAN > 0.0 and opt.netD != "stylegan2":
+            raise NotImplementedError("--gan_mode wgangp --netD %s: the reference's own step dies in cal_gradient_penalty on the list a multiscale "
+                                      "discriminator returns ('list' object has no attribute 'size', networks.py:576); the gradient penalty is "
+                                      "built for --netD stylegan2" % opt.netD)
+        if opt.lambda_G2_GAN > 0.0 and opt.netD2 == "stylegan2":
+            raise NotImplementedError("--gan_mode wgangp --netD2 stylegan2: the reference's StyleGAN2 discriminator of size %d cannot take the "
+                                      "32-pixel tactile patches (stylegan_networks.py:181); run wgangp with --lambda_G2_GAN 0" % opt.crop_size)
+        if opt.lambda_G2_GAN > 0.0:
+            raise NotImplementedError("--gan_mode wgangp with the tactile discriminator (--netD2 %s): the reference's own step dies in "
+                                      "cal_gradient_penalty on the list a multiscale discriminator returns (networks.py:576); run wgangp with "
+                                      "--lambda_G2_GAN 0" % opt.netD2)
+
+    def parallelize(self):
+        from vts import ddp
+        if ddp.active() and self.isTrain and self.opt.gan_mode == "wgangp":
+            raise NotImplementedError("--gan_mode wgangp: not built: data-parallel runs")
+        GraphedStepModel.parallelize(self)
 
     @staticmethod
     def _check_unbuilt_terms(opt, epoch=None):
@@ -842,9 +866,17 @@ class SinSKITGModel(GraphedStepModel):
             elif getattr(self.netD, "is_stylegan2_d", False) or not self._pair:
                 in0, in1 = self._d1_pair(self.real_S, self.fake_I)
                 p_fake_I = dict(in0=in0, in1=in1, real=False, coeff=lam, slot=slot["D_fake_I"], grad_coeff=0.5 * lam)
-                in0, in1 = self._d1_pair(self.real_S, self.real_I)
-                jobs.append((self.netD, [p_fake_I, dict(in0=in0, in1=in1, real=True, coeff=lam, slot=slot["D_real_I"],
-                                                        grad_coeff=0.5 * lam, accumulate=True)]))
+                r0, r1 = self._d1_pair(self.real_S, self.real_I)
+                passes = [p_fake_I, dict(in0=r0, in1=r1, real=True, coeff=lam, slot=slot["D_real_I"], grad_coeff=0.5 * lam, accumulate=True)]
+                if opt.gan_mode == "wgangp":
+                    # cal_gradient_penalty(netD, real_I, fake_I) on the tensors the two passes saw (sinskitG_model.py:1377-1387): behind
+                    # them, not weighted by lambda_G1_GAN, under the 0.5 of loss_D1; alpha is networks.py:568's torch.rand, drawn on the device
+                    injected = self._draws is not None and "gp_alpha" in self._draws
+                    alpha = self._draws["gp_alpha"].to(dev).float().reshape(n) if injected else torch.rand(n, device=dev)
+                    self._gp_alpha = alpha
+                    passes.append(dict(gradient_penalty=True, real=(r0, r1), fake=(in0, in1), alpha=alpha, coeff=1.0, grad_coeff=0.5,
+                                       slot=slot["D_I_grad_penalty"]))
+                jobs.append((self.netD, passes))
             else:   # fake | real batched: rows [0, n) / [n, 2n) of the persistent pair buffers
                 pyr = self._d1_pyramid(2 * n, pool_fake=True)
                 in0, in1 = self._d1_pair(self._S2, self._I2)
@@ -1163,7 +1195,10 @@ class SinSKITGModel(GraphedStepModel):
                      "fake_sample_offset_x", "fake_sample_offset_y")
 
     def _may_use_graphs(self):
-        return GraphedStepModel._may_use_graphs(self) and self._draws is None
+        # injected draws are read from the host every step, so they keep the step eager -- unless the test marks them "device_resident":
+        # float32 device tensors it keeps alive, which a captured segment reads in place (no D2: there are no host-staged ranks)
+        resident = self._draws is not None and self._draws.get("device_resident") and "D2" not in self.model_names
+        return GraphedStepModel._may_use_graphs(self) and (self._draws is None or bool(resident))
 
     def _after_capture(self):
         # the tensors the captured step writes (visuals, predictions, patch stacks): a validation test() in between rebinds these

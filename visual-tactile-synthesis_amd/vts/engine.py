@@ -1737,7 +1737,9 @@ def msd_multi(jobs, criterion, extra=None, extra_cost=0.1, extra_main=False, str
     stat_only=True: a forward-only pass that only RECORDS its BatchNorm statistics; ext_from=<that pass>, ext_after=k splices
     its running-statistics update after group k of this pass (keeps the reference's call order: sinskitG_model.py:1490-1584).
     The first job's first scale (put the full-resolution discriminator first) runs on the launch stream.
-    A StyleGAN2 discriminator (`--netD stylegan2`) in `jobs` runs its passes on the launch stream after the lanes have joined."""
+    A StyleGAN2 discriminator (`--netD stylegan2`) in `jobs` runs its passes on the launch stream after the lanes have joined; among them
+    may be dict(gradient_penalty=True, real=(in0, in1), fake=(in0, in1), alpha, coeff, grad_coeff, slot): sg2d_gradient_penalty, whose
+    weight gradients add to what the passes in front of it left (`gan_mode wgangp`)."""
     sg_jobs = [j for j in jobs if getattr(j[0], "is_stylegan2_d", False)]
     jobs = [j for j in jobs if not getattr(j[0], "is_stylegan2_d", False)]
     if jobs:
@@ -1751,6 +1753,11 @@ def msd_multi(jobs, criterion, extra=None, extra_cost=0.1, extra_main=False, str
 def _sg2d_passes(D, passes, criterion):
     """the pass dictionaries of msd_multi for a single-output StyleGAN2 discriminator"""
     for p in passes:
+        if p.get("gradient_penalty"):      # dict(gradient_penalty=True, real=(in0, in1), fake=(in0, in1), alpha, coeff, grad_coeff, slot)
+            sources = lambda pair: tuple(t for t in pair if t is not None)
+            p["gradients"] = sg2d_gradient_penalty(D, sources(p["real"]), sources(p["fake"]), p["alpha"], p["slot"], coeff=p["coeff"],
+                                                   grad_coeff=p["grad_coeff"], lambda_gp=p.get("lambda_gp", 10.0), constant=p.get("constant", 1.0))
+            continue
         in0, in1 = p["in0"], p.get("in1")
         n, c0, h, w = in0.shape
         if in1 is not None:   # torch.cat([in0, in1], 1) as concat-on-store
@@ -2082,7 +2089,10 @@ def _const(n, v, dev):
 
 
 def _scaled(t, s):
-    """operand t * s (per-(n, c) affine with a constant scale)"""
+    """operand t * s (per-(n, c) affine with a constant scale); s None: t is an operand that carries its affine already"""
+    if s is None:
+        assert isinstance(t, Act)
+        return t
     nc = t.shape[0] * t.shape[1]
     return Act(t, _const(nc, s, t.device), _const(nc, 0.0, t.device))
 
@@ -2109,18 +2119,19 @@ def _sg_layer_forward(m, x, gain=SQRT2, res=None, extra_scale=1.0):
     return y, (t, z, s)
 
 
-def _sg_layer_backward(m, x_shape, saved, g, gain, accumulate, want_dx=True, dx=None, dx_accumulate=False, param_grads=True):
-    """backward of _sg_layer_forward: parameter gradients into .grad, returns the gradient w.r.t. the layer input"""
+def _sg_layer_backward(m, x_shape, saved, g, gain, accumulate, want_dx=True, dx=None, dx_accumulate=False, param_grads=True, bias_grads=True):
+    """backward of _sg_layer_forward: parameter gradients into .grad (bias_grads False: of the weights only), returns the gradient
+    w.r.t. the layer input"""
     from models.stylegan2_blocks import BLUR_KERNEL
     conv, act = m.conv[0], m.act[0]
     t, z, s = saved
     if m.activate:
         dz = ops.bias_act_bwd(g, z, act.bias if act is not None else None, 0.2, gain)
-        if act is not None and param_grads:
+        if act is not None and param_grads and bias_grads:
             ops.channel_sum(dz, act.bias.grad.view(-1), accumulate=accumulate)
     else:
         dz = g
-        if getattr(conv, "bias", None) is not None and param_grads:
+        if getattr(conv, "bias", None) is not None and param_grads and bias_grads:
             ops.channel_sum(dz, conv.bias.grad, accumulate=accumulate)
     if not param_grads:
         pass
@@ -2177,32 +2188,118 @@ def sg2d_forward(D, x, keep=True):
     return out.view(n, 1), ctx
 
 
-def sg2d_backward(D, ctx, dout, accumulate=False, input_grad=False, param_grads=True):
-    """gradients of all parameters into .grad (param_grads); returns d/dx when input_grad"""
+def sg2d_backward(D, ctx, dout, accumulate=False, input_grad=False, param_grads=True, bias_grads=True):
+    """gradients of all parameters into .grad (param_grads; bias_grads False: no bias gradient is touched); returns d/dx when input_grad"""
     l0, l1 = D.final_linear[0], D.final_linear[1]
     c4 = l0.weight.shape[0]
     y_shape, yf, z0, a0, s0, s1l = ctx.lin
     n = dout.shape[0]
     g = dout.reshape(n, 1, 1, 1).contiguous()
-    pg = param_grads
-    if pg:
+    pg, bg = param_grads, param_grads and bias_grads
+    kw = dict(param_grads=pg, bias_grads=bias_grads)
+    if bg:
         ops.channel_sum(g, l1.bias.grad, accumulate=accumulate)
+    if pg:
         ops.wgradk(g, _scaled(a0, s1l), l1.weight.grad.view(1, c4, 1, 1), pad=0, accumulate=accumulate)
     da0 = torch.empty_like(a0)
     ops.convk_bwd_data(_scaled(g, s1l), l1.weight.view(1, c4, 1, 1), da0, pad=0)
     dz0 = ops.bias_act_bwd(da0, z0, l0.bias, 0.2, SQRT2)
-    if pg:
+    if bg:
         ops.channel_sum(dz0, l0.bias.grad, accumulate=accumulate)
+    if pg:
         ops.wgrad4x4(dz0, _scaled(yf, s0), l0.weight.grad, stride=1, pad=0, accumulate=accumulate)
     dyf = torch.empty_like(yf)
     ops.conv4x4(_scaled(dz0, s0), l0.weight, 16, c4 * 16, c4, dyf, stride=1, pad=0, transposed=True)
-    g = _sg_layer_backward(D.final_conv, y_shape, ctx.final, dyf, SQRT2, accumulate, param_grads=pg)
+    g = _sg_layer_backward(D.final_conv, y_shape, ctx.final, dyf, SQRT2, accumulate, **kw)
     blocks = list(D.convs)[1:]
     for blk, (x_shape, s1, y1_shape, s2, ss) in zip(reversed(blocks), reversed(ctx.blocks)):
-        dy1 = _sg_layer_backward(blk.conv2, y1_shape, s2, g, 1.0, accumulate, param_grads=pg)
-        dx = _sg_layer_backward(blk.skip, x_shape, ss, g, 1.0, accumulate, param_grads=pg)
-        g = _sg_layer_backward(blk.conv1, x_shape, s1, dy1, SQRT2, accumulate, dx=dx, dx_accumulate=True, param_grads=pg)
-    return _sg_layer_backward(D.convs[0], ctx.x_shape, ctx.first, g, SQRT2, accumulate, want_dx=input_grad, param_grads=pg)
+        dy1 = _sg_layer_backward(blk.conv2, y1_shape, s2, g, 1.0, accumulate, **kw)
+        dx = _sg_layer_backward(blk.skip, x_shape, ss, g, 1.0, accumulate, **kw)
+        g = _sg_layer_backward(blk.conv1, x_shape, s1, dy1, SQRT2, accumulate, dx=dx, dx_accumulate=True, **kw)
+    return _sg_layer_backward(D.convs[0], ctx.x_shape, ctx.first, g, SQRT2, accumulate, want_dx=input_grad, **kw)
+
+
+# ---- WGAN-GP gradient penalty on the StyleGAN2 discriminator (reference models/networks.py:550-583, cal_gradient_penalty 'mixed') ----
+# The discriminator is piecewise linear in its input and couples no samples (its minibatch-stddev branch is off: stylegan_networks.py:
+# 744, 769), so with g = dD(x^)/dx^ (dout = 1), P = lambda / N sum_n (||g_n + 1e-16|| - c)^2 and v = dP/dg the parameter gradient of P is the
+# ordinary first-order weight gradient with every layer INPUT replaced by the tangent of v pushed forward through the network (same
+# convolutions, no biases, each activation replaced by its derivative at the saved pre-activation) under the backward signals of
+# dout = 1:  dP/dW_k = delta_k (x) t_{k-1}.  No bias receives a gradient.  Forward over reverse instead of autograd's double backward:
+# the penalty runs on the discriminator's own conv / FIR / bias_act_bwd / weight-gradient kernels.
+def _sg_layer_tangent(m, tx, saved, gain=SQRT2, tres=None, extra_scale=1.0):
+    """tangent of _sg_layer_forward at its saved pre-activation: (tangent output, saved in the layer's format with the tangent input)"""
+    from models.stylegan2_blocks import BLUR_KERNEL
+    conv, act = m.conv[0], m.act[0]
+    _, z, _ = saved
+    first = isinstance(tx, Act)             # the cotangent v = Act(g, scale, shift): it carries the layer's operand scale itself
+    assert not (first and m.downsample)
+    tt = ops.upfirdn2d(tx, BLUR_KERNEL, pad=m.blur_pad) if m.downsample else tx
+    s = None if first else extra_scale / (m.cin * m.k * m.k) ** 0.5
+    tz = torch.empty_like(z)
+    if m.downsample:
+        ops.convk_s2(_scaled(tt, s), conv.weight, tz)
+    else:
+        ops.convk(_scaled(tt, s), conv.weight, tz, pad=m.k // 2)
+    if m.activate:
+        ty = ops.bias_act_bwd(tz, z, act.bias if act is not None else None, 0.2, gain)
+        if tres is not None:
+            ty = ops.pad_affine(ty, (0, 0, 0, 0), 0, res=tres)
+    else:
+        assert tres is None
+        ty = tz
+    return ty, (tt, z, s)
+
+
+def sg2d_first_scale(D):
+    """the equalised-lr operand scale of the discriminator's first convolution"""
+    m = D.convs[0]
+    return 1.0 / (m.cin * m.k * m.k) ** 0.5
+
+
+def sg2d_tangent_forward(D, ctx, v):
+    """Pushes the input tangent v through the discriminator linearised at ctx (of sg2d_forward(keep=True)), layer by layer: Blur where
+    the layer downsamples, the same convolution with the same operand scale and no bias, bias_act_bwd at the saved pre-activation in
+    place of the activation (plus the skip branch's tangent where bias_act took `res`), the EqualLinear pair likewise.
+    v: a tensor [N, C, size, size], or an Act whose affine ALREADY includes sg2d_first_scale(D) (the cotangent of vts_gp_penalty applied on
+    load).  Returns an Sg2dCtx whose saved layer inputs are the tangents and whose pre-activations are ctx's: sg2d_backward on it under
+    the same dout gives d<v, dD/dx> / d weights."""
+    tc = Sg2dCtx()
+    tc.x_shape = ctx.x_shape
+    ty, tc.first = _sg_layer_tangent(D.convs[0], v, ctx.first)
+    tc.blocks = []
+    for blk, (x_shape, s1, y1_shape, s2, ss) in zip(list(D.convs)[1:], ctx.blocks):
+        ty1, t1 = _sg_layer_tangent(blk.conv1, ty, s1)
+        tsk, ts = _sg_layer_tangent(blk.skip, ty, ss, extra_scale=1.0 / SQRT2)
+        ty, t2 = _sg_layer_tangent(blk.conv2, ty1, s2, gain=1.0, tres=tsk)
+        tc.blocks.append((x_shape, t1, y1_shape, t2, ts))
+    tyf, tc.final = _sg_layer_tangent(D.final_conv, ty, ctx.final)
+    l0 = D.final_linear[0]
+    c4 = l0.weight.shape[0]
+    y_shape, _, z0, _, s0, s1l = ctx.lin
+    tz0 = torch.empty_like(z0)
+    ops.conv4x4(_scaled(tyf, s0), l0.weight, c4 * 16, 16, c4, tz0, stride=1, pad=0)
+    ta0 = ops.bias_act_bwd(tz0, z0, l0.bias, 0.2, SQRT2)
+    tc.lin = (y_shape, tyf, z0, ta0, s0, s1l)
+    return tc
+
+
+def sg2d_gradient_penalty(D, real, fake, alpha, slot, coeff=1.0, grad_coeff=1.0, lambda_gp=10.0, constant=1.0, param_grads=True):
+    """cal_gradient_penalty(netD, real, fake, type='mixed', constant, lambda_gp) (networks.py:550-583) for the StyleGAN2 discriminator.
+    real / fake: a tensor [N, C, size, size] or a tuple of up to two concat sources (ops.gp_interp); alpha: device [N].
+    coeff * penalty is added to the loss slot `slot`; with param_grads, grad_coeff * d penalty / d weights is ADDED to every weight's
+    .grad (no bias .grad is touched: those gradients are exactly zero).  Returns g = dD(x^)/dx^ [N, C, size, size] over all channels
+    (the reference's `gradients`).  Launches only; capturable; a second call gives the same bits.
+    Two-pass form: the (dout = 1) backward-data chain runs once for g and once more under the tangents."""
+    xh = ops.gp_interp(real, fake, alpha)
+    n = xh.shape[0]
+    ones = _const(n, 1.0, xh.device)
+    _, ctx = sg2d_forward(D, xh, keep=True)
+    g = sg2d_backward(D, ctx, ones, input_grad=True, param_grads=False)
+    scale, shift = ops.gp_penalty(g, slot, coeff, grad_coeff * sg2d_first_scale(D), lambda_gp=lambda_gp, constant=constant)
+    if param_grads:
+        tctx = sg2d_tangent_forward(D, ctx, Act(g, scale, shift))
+        sg2d_backward(D, tctx, ones, accumulate=True, param_grads=True, bias_grads=False, input_grad=False)
+    return g
 
 
 _SG_BUF = {}

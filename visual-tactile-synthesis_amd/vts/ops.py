@@ -1178,6 +1178,50 @@ def l1(a, b, coeff, loss_slot, grad=None, accumulate=False):
             "vts_l1")
 
 
+def _cat_source(t, hw):
+    """(pointer, sample stride, channels) of a concat source: a contiguous NCHW tensor or a channel slice of a wider one"""
+    if t is None:
+        return None, 0, 0
+    assert t.dtype == torch.float32 and t.is_cuda and (t.shape[1] == 1 or t.stride(1) == hw) and t[0].is_contiguous(), "a concat source is a channel slice"
+    return t.data_ptr(), t.stride(0) if t.shape[0] > 1 else t.shape[1] * hw, t.shape[1]
+
+
+def gp_interp(real, fake, alpha, out=None):
+    """out[n] = alpha[n] * cat(real)[n] + (1 - alpha[n]) * cat(fake)[n]  (cal_gradient_penalty 'mixed', networks.py:568-571).
+    real / fake: a tensor or a tuple of one or two concat sources [N, c, H, W] (channel slices of wider buffers are read in place);
+    alpha: device [N]."""
+    real = tuple(real) if isinstance(real, (tuple, list)) else (real,)
+    fake = tuple(fake) if isinstance(fake, (tuple, list)) else (fake,)
+    assert 1 <= len(real) <= 2 and 1 <= len(fake) <= 2
+    n, _, h, w = real[0].shape
+    c = sum(t.shape[1] for t in real)
+    assert all(t.shape[0] == n and tuple(t.shape[2:]) == (h, w) for t in real + fake) and c == sum(t.shape[1] for t in fake)
+    assert alpha.dtype == torch.float32 and alpha.numel() == n and alpha.is_contiguous()
+    if out is None:
+        out = torch.empty(n, c, h, w, dtype=torch.float32, device=real[0].device)
+    assert out.shape == (n, c, h, w) and out.is_contiguous()
+    src = [v for side in (real, fake) for t in (side + (None,))[:2] for v in _cat_source(t, h * w)]
+    _run("gp_interp", 12.0 * out.numel(), 3.0 * out.numel(), L.load().vts_gp_interp, *src, alpha.data_ptr(), n, h * w, out.data_ptr(), L.stream())
+    return out
+
+
+def gp_penalty(g, loss_slot, coeff, grad_coeff, lambda_gp=10.0, constant=1.0, value=None, ws=None, out=None):
+    """The penalty lambda / N sum_n (||g_n + 1e-16|| - constant)^2 of g [N, C, H, W] (networks.py:578-582): coeff * penalty is added to
+    the loss slot (and the plain value stored into value[0], when given); returns (scale, shift), the per-(n, c) operand affine with
+    grad_coeff * d penalty / dg = Act(g, scale, shift) (written into `out` = (scale, shift) when given)."""
+    lib = L.load()
+    assert g.dtype == torch.float32 and g.is_contiguous() and (loss_slot is None or loss_slot.dtype == torch.int64)
+    n, c = g.shape[0], g.shape[1]
+    m = g.numel() // n
+    if ws is None:
+        ws = workspace(lib.vts_gp_penalty_ws_floats(n, m), g.device)      # (the partials are doubles: the lane's scratch is aligned)
+    scale, shift = out if out is not None else (torch.empty(n * c, dtype=torch.float32, device=g.device) for _ in range(2))
+    assert scale.numel() == n * c and shift.numel() == n * c
+    _run("gp_penalty", 4.0 * g.numel(), 2.0 * g.numel(), lib.vts_gp_penalty, g.data_ptr(), n, m, c, lambda_gp, constant, coeff, grad_coeff,
+         L.ptr(loss_slot), L.ptr(value), scale.data_ptr(), shift.data_ptr(), ws.data_ptr(), L.stream())
+    return scale, shift
+
+
 def patch_gather(src, img, offx, offy, size, out, c0=0, channels=None):
     lib = L.load()
     c = src.shape[1] if channels is None else channels
